@@ -11,10 +11,18 @@ One *step* = one pass of the hot path over one batch that is already resident in
 Frames are independent units, so N GPUs = N ranks each with its own 32 frames (weak scaling), no collective
 on the data path; torch.distributed (RCCL) is used only for the timing barrier and the MAX over ranks.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--full` adds everything else the
+benchmark measures or checks, outside the timed steps:
+  value_windows the same K-step window nine more times (`--windows`)
+  batch_consistency  the last timed step's people lists against independent batch-2 passes
   roofline      dominant kernel (by time): algorithmic FLOPs of its launches / their HIP-event duration, every launch
                 timed once in plan order (agrees with rocprofv3 `--lanes 1`); `back_to_back` = four repeats per launch
+  decode, pcie_inclusive, the extra sections (other dtypes, D-54, decode stress, training shard, agreement with the
+                reference pipeline's people)
   cpu_baseline  the CPU oracle (torch-CPU fp32 forward + NumPy decode) on a bounded sample, N=1 only
+The `--no-*` switches trim a `--full` run.  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (float32 / float64): the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -96,7 +104,7 @@ def mfma_busy(kernel_name, achieved_tflops, peak_tflops):
            "mfma_busy_conv_stack": d.get("conv_stack_mfma_busy"),
            "mfma_busy_source": os.path.basename(files[-1]),
            "mfma_busy_provenance": ("a COMMITTED constant, not measured by this run: SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 x "
-                                    "1024 SIMDs), one rocprofv3 --kernel-trace --pmc pass of `python3 bench.py --lanes 1 --shared-plan "
+                                    "1024 SIMDs), one rocprofv3 --kernel-trace --pmc pass of `python3 bench.py --full --lanes 1 --shared-plan "
                                     "--no-extras --no-verify --no-cpu-baseline` (tools/pmc_mfma.sh, file date " + str(d.get("_date")) +
                                     "); `mfma_busy` = this kernel, `mfma_busy_conv_stack` = stem + all convolutions + head, time-weighted"),
            "held_clock_ghz": held,
@@ -177,6 +185,37 @@ def _fail_hook(rank):
         raise RuntimeError(f"PPN_BENCH_FAIL_RANK: rank {rank} fails on request")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs DIR`: each array as DIR/<name>.npy, floating point kept as float32 / float64, integer indices and
+    counts as float64 (exact); at most DUMP_LIMIT_BYTES in all."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a, dtype=a.dtype if a.dtype in (np.float32, np.float64) else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def decode_arrays(res):
+    """The compact people lists of a DecodeResult as fixed-shape host arrays: slots at or beyond an image's count hold
+    -1 (indices) / 0 (boxes, scores), so that two runs compare element for element."""
+    cnt = res.count.cpu().numpy().astype(np.int64)
+    live = np.arange(res.max_humans)[None, :] < np.minimum(cnt, res.max_humans)[:, None]      # [B, max_humans]
+    arrs = {"count": cnt}
+    for name, fill in (("kp_cell", -1), ("limb_arg", -1), ("bbox", 0), ("score", 0)):
+        a = getattr(res, name).cpu().numpy()
+        m = live.reshape(live.shape + (1,) * (a.ndim - 2))
+        arrs[name] = np.where(m, a, np.array(fill, dtype=a.dtype))
+    return arrs
+
+
 def main_train(args):
     """--workload train: BASELINE configs[3] per-GPU shard -- one PPNTrainer.train_step per step (train-mode forward,
     PPNLoss fwd+bwd, backward, GradNorm probes + task-weight step, gradient all-reduce over RCCL, Adam)."""
@@ -240,6 +279,14 @@ def main_train(args):
     t_local = fence()
     dt = time.perf_counter() - t0
     exposed = T_.BucketedAllReduce.exposed_ms()
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the last timed step receives (losses, task weights) and a fixed, seeded sample of the
+        # parameters it left behind (the whole flat buffer is above the dump limit)
+        n = tr.flat.numel()
+        idx = np.unique(np.random.default_rng(0).integers(0, n, size=min(n, 1 << 21)))
+        dump_outputs(args.dump_outputs, {
+            "losses": losses.float().cpu().numpy(), "task_weights": w.float().cpu().numpy(),
+            "params_sample": tr.flat[torch.from_numpy(idx).to(tr.flat.device)].cpu().numpy()})
     per_rank = _per_rank_stats(dist, backend, dev, world, B * args.steps / (t_local - t0),
                                (sum(exposed) / len(exposed)) if exposed else 0.0)
     if dist is not None:
@@ -278,7 +325,7 @@ def main_train(args):
                 "time the main stream sits idle in BucketedAllReduce.finish() until the last gradient bucket has arrived (two "
                 "timing events around the waits), mean over the timed steps, per rank: what the exchange adds to the step "
                 "beyond what ran under the backward")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline_train(args.arch, S)
         print(json.dumps(result), flush=True)
     if dist is not None:
@@ -712,8 +759,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=10,
-                    help="timing windows of --steps steps each (the first is `value`; all go into `value_windows`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (extra timing windows, batch-consistency "
+                         "check, per-launch roofline, decode and PCIe-inclusive rates, extra sections, CPU baseline); "
+                         "the --no-* switches trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timing windows of --steps steps each (the first is `value`; all go into `value_windows`); "
+                         "default 10 with --full, else 1")
     ap.add_argument("--batch", type=int, default=32, help="frames per GPU")
     ap.add_argument("--size", type=int, default=384)
     ap.add_argument("--arch", default="drn_d_22")
@@ -728,7 +782,7 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the extra sections (materialized_head, decode_stress, f32_parity_mode, d54_end_to_end, "
                          "train_shard) reported beside the headline at N=1")
-    ap.add_argument("--layers", action="store_true", help="print the per-layer table to stderr")
+    ap.add_argument("--layers", action="store_true", help="print the per-layer table to stderr (implies --full)")
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("PPN_LANES", "2")),
                     help="stream lanes successive steps alternate between (rt.MultiLaneInference); 1 = one lane with "
                          "the same kernels (what the rocprofv3 per-kernel durations are compared with).  Default 2 since round 5: "
@@ -749,6 +803,9 @@ def main():
                     help="write the f32 head tensor [B,7605,24,24] and decode it with the stand-alone arg-max kernel "
                          "(model.forward + get_humans_by_feature path) instead of the fused inference path")
     args = ap.parse_args()
+    args.full = args.full or args.layers
+    if args.windows is None:
+        args.windows = 10 if args.full else 1
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         self_launch(sys.argv[1:], args.gpus)
     if args.workload == "train":
@@ -841,7 +898,12 @@ def main():
     value = world * B * args.steps / dt
     people = int(out.count.sum().item())
     last_frames = frame_sets[(step_no[0] - 1) % NROT]            # what the last timed step read
-    if fused and rank == 0 and not args.no_verify:
+    if rank == 0 and args.dump_outputs:
+        # the people lists a caller receives from the last timed step, read before anything below reuses the buffers
+        if getattr(out, "ready", None) is not None:
+            out.ready.synchronize()
+        dump_outputs(args.dump_outputs, decode_arrays(out))
+    if fused and rank == 0 and args.full and not args.no_verify:
         # `out` lives in its lane's / decoder's buffers: read it before the extra timing windows below reuse them
         if getattr(out, "ready", None) is not None:
             out.ready.synchronize()
@@ -868,78 +930,6 @@ def main():
 
     result = None
     if rank == 0:
-        # the people lists of the last timed step, checked before anything else reuses the lanes' buffers
-        if out_host_early is not None:
-            class _Held:                               # the early host copy of the last timed step's result
-                ready = None
-
-                @staticmethod
-                def to_host():
-                    return out_host_early
-            out = _Held
-        verified = verify_against_slices(net, last_frames, out) if (fused and B % 2 == 0 and not args.no_verify) else None
-        # ---- per-kernel durations: HIP events on the launch stream around every launch ----------------
-        # per-launch durations with one launch in flight (what rocprofv3 shows for `--lanes 1`)
-        # Primary figures: every launch ONCE in plan order (in sequence: each launch finds the caches as the previous
-        # layer left them -- what rocprofv3 `--lanes 1` averages).  Secondary (`back_to_back`): four repeats of the same
-        # launch between its two events, i.e. warm caches and no launch gap, the figure round 1 quoted (~5 % higher).
-        agg, table, agg4 = {}, [], {}
-        reps = 5
-        # the same plan flags as the timed path (a multi-lane plan leaves out the filter-bank kernel and the lone-launch
-        # tiles): the per-launch figures describe the kernels `value` ran
-        pflags = getattr(pipe, "_conv_flags", 0) if pipe is not None else 0
-        net.profile_layers(frames, src_is_u8=True, repeats=1, fused_decode=fused, conv_flags=pflags)   # untimed: first direct launches
-        for r in range(reps):
-            for name, kern, ms, fl in net.profile_layers(frames, src_is_u8=True, repeats=1, fused_decode=fused, conv_flags=pflags):
-                a = agg.setdefault(kern, [0.0, 0.0, 0])
-                a[0] += ms; a[1] += fl; a[2] += 1
-                if r == 0:
-                    table.append((name, kern, ms, fl))
-            for name, kern, ms, fl in net.profile_layers(frames, src_is_u8=True, repeats=4, fused_decode=fused, conv_flags=pflags):
-                a = agg4.setdefault(kern, [0.0, 0.0, 0])
-                a[0] += ms; a[1] += fl; a[2] += 1
-        # An event pair around ONE launch also spans the marker and launch latency (6-7 us around an empty kernel on
-        # this stack; rocprofv3's begin-to-end durations do not contain it): calibrated here on a 64-byte fill and
-        # subtracted per launch, so that `avg_launch_us` is comparable with the rocprofv3 summary under profiles/.
-        probe = torch.zeros(16, device=dev)
-        pe = [torch.cuda.Event(enable_timing=True) for _ in range(100)]
-        for i in range(50):
-            pe[2 * i].record(); probe.zero_(); pe[2 * i + 1].record()
-        torch.cuda.synchronize(dev)
-        ev_over_ms = min(pe[2 * i].elapsed_time(pe[2 * i + 1]) for i in range(10, 50))
-        raw_dom = max(agg.items(), key=lambda kv: kv[1][0])
-        raw_us = raw_dom[1][0] / raw_dom[1][2] * 1e3
-        for a in agg.values():
-            a[0] = max(a[0] - a[2] * ev_over_ms, 1e-6)
-        fwd_ms = sum(a[0] for a in agg.values()) / reps
-        fwd_flops = sum(a[1] for a in agg.values()) / reps
-        dom = max(agg.items(), key=lambda kv: kv[1][0])
-        dk, (dms, dfl, dn) = dom
-        # f16 MFMA = the bf16 rate; f16x3 spends three f16 MFMAs per algorithmic multiply-add: a third of it
-        peak = (F32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else
-                BF16_DENSE_PEAK_TFLOPS / 3.0 if args.dtype == "f16x3" else BF16_DENSE_PEAK_TFLOPS)
-        achieved = dfl / (dms * 1e-3) / 1e12
-        if args.layers:
-            for name, kern, ms, fl in table:
-                print(f"{name:28s} {ms*1e3:9.1f} us {fl/ms/1e9 if ms > 0 else 0:9.1f} TFLOP/s  {kern}", file=sys.stderr)
-        # decode kernels: dense bytes of the head read once
-        # median of seven calls behind two untimed ones (the first call of a Decoder sets kernel attributes)
-        if fused:
-            unary, keys = net.forward_u8(frames, fused_decode=True)
-            dfn = lambda: dec.decode_fused(unary, keys)                  # noqa: E731
-        else:
-            head = net.forward_u8(frames)
-            dfn = lambda: dec(head)                                      # noqa: E731
-        dfn(); dfn()
-        torch.cuda.synchronize(dev)
-        dts = []
-        for _ in range(7):
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            ev[0].record(); dfn(); ev[1].record()
-            torch.cuda.synchronize(dev)
-            dts.append(ev[0].elapsed_time(ev[1]))
-        dec_ms = sorted(dts)[3]
-        head_bytes = B * cfg.lastsize() * (S // 16) * (S // 16) * 4
         result = {
             "metric": "images/sec (384x384, DRN-D-22) at 1/2/4/8 MI355X",
             "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
@@ -978,131 +968,206 @@ def main():
                        "parallelism": f"frames sharded over {world} GPU(s), no data-path collective"},
             "rccl_ranks": world if (dist is not None and backend == "nccl") else (1 if world == 1 else 0),
             **({"per_rank": per_rank["rates"]} if per_rank is not None else {}),
-            "roofline": {"bound": "mfma", "kernel": dk, "launches_per_step": dn // reps,
-                         "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4),
-                         "timing": "HIP events on the launch stream around every launch of one pass over the plan, one "
-                                   "launch in flight, in sequence (as rocprofv3 `--lanes 1`; with several lanes dispatches "
-                                   "share the GPU and each one's begin-to-end time grows); the event pair's own "
-                                   "marker + launch latency, calibrated on an empty kernel, is subtracted per launch",
-                         "event_overhead_us": round(ev_over_ms * 1e3, 2), "avg_launch_us_raw": round(raw_us, 2),
-                         "back_to_back": {"what": "the same launches, four repeats between the two events (warm caches)",
-                                          "avg_launch_us": round(agg4[dk][0] / agg4[dk][2] * 1e3, 2),
-                                          "frac": round(agg4[dk][1] / (agg4[dk][0] * 1e-3) / 1e12 / peak, 4)},
-                         "traffic": (pmc_traffic(dk) or {}).get("bytes_per_launch"),
-                         "traffic_source": (pmc_traffic(dk) or {}).get("source"),
-                         "traffic_provenance": ("a COMMITTED constant, not measured by this run: HBM bytes per launch of this "
-                                                "kernel from two separate rocprofv3 --pmc passes (FETCH_SIZE x 2 + WRITE_SIZE, "
-                                                "--lanes 1) of `python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline "
-                                                "--no-extras --no-verify --lanes 1`, tools/pmc_bench.sh -> "
-                                                "tools/pmc_traffic_summary.py -> profiles/" +
-                                                str((pmc_traffic(dk) or {}).get("source")) + " (file date " +
-                                                str((pmc_traffic(dk) or {}).get("date")) + "); bench.py cannot run the profiler on itself"),
-                         "avg_launch_us": round(dms / dn * 1e3, 2),
-                         "flops_per_launch_avg": round(dfl / dn),
-                         **mfma_busy(dk, achieved, peak)},
-            "step_tflops": round(fwd_flops / ms_per_step / 1e9, 2),      # conv FLOPs / whole-step time (lanes overlap)
-            "conv_stack": {"ms": round(fwd_ms, 4), "tflops": round(fwd_flops / fwd_ms / 1e9, 2),
-                           "frac_of_mfma_peak": round(fwd_flops / fwd_ms / 1e9 / peak, 4),
-                           "gflop_per_image": round(fwd_flops / B / 1e9, 3)},
-            "decode": ({"mode": "fused into the head conv epilogue (no head tensor); NMS + limb parse kernel only",
-                        "ms": round(dec_ms, 4), "people": people} if fused else
-                       {"mode": "stand-alone: dense limb arg-max over the materialised head + NMS + limb parse",
-                        "ms": round(dec_ms, 4), "gbps": round(head_bytes / dec_ms / 1e6, 1),
-                        "frac_of_hbm_peak": round(head_bytes / dec_ms / 1e6 / 8000.0, 4), "people": people}),
         }
-        if world == 1:
-            # PCIe-inclusive rate (NOT `value`): every step first copies the u8 frames from pinned host memory and
-            # ends with the compact decode result (counts, cells, boxes, scores) back on the host.
-            host = torch.from_numpy(prng.u8_frames(1234, B, (S, S))).pin_memory()
-            n = max(6, args.steps)
-            if pipe is not None:                 # untimed: every lane allocates its pinned read-back buffers once
-                for r in [pipe.submit(host, to_host=True) for _ in range(max(1, args.lanes))]:
-                    r.ready.synchronize()
-            torch.cuda.synchronize(dev)
-            # the two copies alone (no compute queued): says whether a low PCIe-inclusive rate is the link / the NUMA
-            # placement of the pinned pages on this box, or the pipeline
-            h2d_dst = torch.empty_like(host, device=dev)
-            h2d_dst.copy_(host, non_blocking=True)
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            for _ in range(10):
-                h2d_dst.copy_(host, non_blocking=True)
-            torch.cuda.synchronize(dev)
-            h2d_ms = (time.perf_counter() - t0) / 10 * 1e3
-            del h2d_dst
-            t1 = time.perf_counter()
-            if pipe is not None:
-                # pinned frames -> the lane's own input buffer (H2D on the lane's stream) -> step -> the compact result
-                # into the lane's pinned buffers (D2H behind the decode); the host unpacks batch i - lanes + 1 while the
-                # later batches run: no synchronous copy anywhere
-                pending = []
-                host_s = [0.0, 0.0, 0.0]             # host seconds in submit / waiting on the ready event / unpack
+        if args.full:
+            # the people lists of the last timed step, checked before anything else reuses the lanes' buffers
+            if out_host_early is not None:
+                class _Held:                               # the early host copy of the last timed step's result
+                    ready = None
 
-                def collect(r):
-                    ta = time.perf_counter()
-                    r.ready.synchronize()
-                    tb = time.perf_counter()
-                    out = r.hosted.unpack()
-                    host_s[1] += tb - ta
-                    host_s[2] += time.perf_counter() - tb
-                    return out
-
-                for it in range(n):
-                    ta = time.perf_counter()
-                    pending.append(pipe.submit(host, to_host=True))
-                    host_s[0] += time.perf_counter() - ta
-                    if len(pending) == max(1, args.lanes):
-                        hosted = collect(pending.pop(0))
-                for r in pending:
-                    hosted = collect(r)
-                pcie_people = sum(h["n"] for h in hosted)
+                    @staticmethod
+                    def to_host():
+                        return out_host_early
+                out = _Held
+            verified = verify_against_slices(net, last_frames, out) if (fused and B % 2 == 0 and not args.no_verify) else None
+            # ---- per-kernel durations: HIP events on the launch stream around every launch ----------------
+            # per-launch durations with one launch in flight (what rocprofv3 shows for `--lanes 1`)
+            # Primary figures: every launch ONCE in plan order (in sequence: each launch finds the caches as the previous
+            # layer left them -- what rocprofv3 `--lanes 1` averages).  Secondary (`back_to_back`): four repeats of the same
+            # launch between its two events, i.e. warm caches and no launch gap, the figure round 1 quoted (~5 % higher).
+            agg, table, agg4 = {}, [], {}
+            reps = 5
+            # the same plan flags as the timed path (a multi-lane plan leaves out the filter-bank kernel and the lone-launch
+            # tiles): the per-launch figures describe the kernels `value` ran
+            pflags = getattr(pipe, "_conv_flags", 0) if pipe is not None else 0
+            net.profile_layers(frames, src_is_u8=True, repeats=1, fused_decode=fused, conv_flags=pflags)   # untimed: first direct launches
+            for r in range(reps):
+                for name, kern, ms, fl in net.profile_layers(frames, src_is_u8=True, repeats=1, fused_decode=fused, conv_flags=pflags):
+                    a = agg.setdefault(kern, [0.0, 0.0, 0])
+                    a[0] += ms; a[1] += fl; a[2] += 1
+                    if r == 0:
+                        table.append((name, kern, ms, fl))
+                for name, kern, ms, fl in net.profile_layers(frames, src_is_u8=True, repeats=4, fused_decode=fused, conv_flags=pflags):
+                    a = agg4.setdefault(kern, [0.0, 0.0, 0])
+                    a[0] += ms; a[1] += fl; a[2] += 1
+            # An event pair around ONE launch also spans the marker and launch latency (6-7 us around an empty kernel on
+            # this stack; rocprofv3's begin-to-end durations do not contain it): calibrated here on a 64-byte fill and
+            # subtracted per launch, so that `avg_launch_us` is comparable with the rocprofv3 summary under profiles/.
+            probe = torch.zeros(16, device=dev)
+            pe = [torch.cuda.Event(enable_timing=True) for _ in range(100)]
+            for i in range(50):
+                pe[2 * i].record(); probe.zero_(); pe[2 * i + 1].record()
+            torch.cuda.synchronize(dev)
+            ev_over_ms = min(pe[2 * i].elapsed_time(pe[2 * i + 1]) for i in range(10, 50))
+            raw_dom = max(agg.items(), key=lambda kv: kv[1][0])
+            raw_us = raw_dom[1][0] / raw_dom[1][2] * 1e3
+            for a in agg.values():
+                a[0] = max(a[0] - a[2] * ev_over_ms, 1e-6)
+            fwd_ms = sum(a[0] for a in agg.values()) / reps
+            fwd_flops = sum(a[1] for a in agg.values()) / reps
+            dom = max(agg.items(), key=lambda kv: kv[1][0])
+            dk, (dms, dfl, dn) = dom
+            # f16 MFMA = the bf16 rate; f16x3 spends three f16 MFMAs per algorithmic multiply-add: a third of it
+            peak = (F32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else
+                    BF16_DENSE_PEAK_TFLOPS / 3.0 if args.dtype == "f16x3" else BF16_DENSE_PEAK_TFLOPS)
+            achieved = dfl / (dms * 1e-3) / 1e12
+            if args.layers:
+                for name, kern, ms, fl in table:
+                    print(f"{name:28s} {ms*1e3:9.1f} us {fl/ms/1e9 if ms > 0 else 0:9.1f} TFLOP/s  {kern}", file=sys.stderr)
+            # decode kernels: dense bytes of the head read once
+            # median of seven calls behind two untimed ones (the first call of a Decoder sets kernel attributes)
+            if fused:
+                unary, keys = net.forward_u8(frames, fused_decode=True)
+                dfn = lambda: dec.decode_fused(unary, keys)                  # noqa: E731
             else:
-                for it in range(n):
-                    frames.copy_(host, non_blocking=True)
-                    hosted = step().to_host()
-                pcie_people = sum(h["n"] for h in hosted)
+                head = net.forward_u8(frames)
+                dfn = lambda: dec(head)                                      # noqa: E731
+            dfn(); dfn()
             torch.cuda.synchronize(dev)
-            dt1 = time.perf_counter() - t1
-            result["pcie_inclusive"] = {"value": round(B * n / dt1, 2), "unit": "images/sec",
-                                        "ms_per_step": round(dt1 / n * 1e3, 4), "h2d_bytes_per_step": host.numel(),
-                                        "host_ms_per_step": ({k: round(v / n * 1e3, 4) for k, v in
-                                                              zip(("submit", "wait", "unpack"), host_s)}
-                                                             if pipe is not None else None),
-                                        "h2d_alone_ms": round(h2d_ms, 4),
-                                        "h2d_alone_gbps": round(host.numel() / h2d_ms / 1e6, 2),
-                                        "people": int(pcie_people),
-                                        "slow_mode": bool(B * n / dt1 < 0.75 * value),
-                                        "slow_mode_note": "true = this process ran the PCIe loop in the slow mode seen on some boxes / processes "
-                                                          "(< 0.75 of `value` although h2d_alone_gbps is normal: host submit or GPU-side "
-                                                          "wait 2-3x the usual, profiles/r03/pcie_modes_sdma.txt); `value` is unaffected "
-                                                          "(frames resident in HBM)",
-                                        "note": "per step: H2D of the pinned u8 frames into the lane's input buffer, the "
-                                                "step, D2H of the compact result (first 64 people slots per image) into pinned "
-                                                "buffers, all queued on the lane's stream; the host unpacks a batch while the "
-                                                "next ones run"}
-        if world == 1 and not args.no_extras:
-            if pipe is not None:
-                pipe.close()
-            result.update(extra_sections(args, dev, net, frames, dec))
-        # what `value` is worth in the TASK metric, right beside it: the timed mode's people against the reference pipeline's
-        # (8 calibrated frames, the reference's own matcher; `ap_vs_reference` / `bf16_agreement` hold the details)
-        apv, agr = result.get("ap_vs_reference", {}), result.get("bf16_agreement", {})
-        if args.dtype == "bf16" and "bf16" in apv and "reproduced_exactly" in agr:
-            result["value_fidelity"] = {"total_ap": apv["bf16"][-1], "ap_ceiling": apv["self"][-1],
-                                        "reference_people_reproduced_exactly": f"{agr['reproduced_exactly']}/{agr['reference_people']}",
-                                        "same_root": f"{agr['same_root']}/{agr['reference_people']}",
-                                        "task_equivalent": bool(agr["reproduced_exactly"] >= 0.97 * agr["reference_people"]),
-                                        "modes_that_are": "float16x3 (`f16x3_mode`), float32 (`f32_parity_mode`): all people, AP = ceiling"}
-        if verified is not None:
-            if "bf16_agreement" in result or "reference_agreement" in result:
-                ra = result.get("reference_agreement", result.get("bf16_agreement"))
-                verified["reference_agreement"] = {k: ra[k] for k in ("reference_people", "reproduced_exactly", "same_root",
-                                                                      "same_root_frac", "keypoint_cell_agreement")
-                                                   if k in ra}
-            result["batch_consistency"] = verified
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(args.arch, 4, S)
+            dts = []
+            for _ in range(7):
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ev[0].record(); dfn(); ev[1].record()
+                torch.cuda.synchronize(dev)
+                dts.append(ev[0].elapsed_time(ev[1]))
+            dec_ms = sorted(dts)[3]
+            head_bytes = B * cfg.lastsize() * (S // 16) * (S // 16) * 4
+            result.update({
+                "roofline": {"bound": "mfma", "kernel": dk, "launches_per_step": dn // reps,
+                             "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                             "frac": round(achieved / peak, 4),
+                             "timing": "HIP events on the launch stream around every launch of one pass over the plan, one "
+                                       "launch in flight, in sequence (as rocprofv3 `--lanes 1`; with several lanes dispatches "
+                                       "share the GPU and each one's begin-to-end time grows); the event pair's own "
+                                       "marker + launch latency, calibrated on an empty kernel, is subtracted per launch",
+                             "event_overhead_us": round(ev_over_ms * 1e3, 2), "avg_launch_us_raw": round(raw_us, 2),
+                             "back_to_back": {"what": "the same launches, four repeats between the two events (warm caches)",
+                                              "avg_launch_us": round(agg4[dk][0] / agg4[dk][2] * 1e3, 2),
+                                              "frac": round(agg4[dk][1] / (agg4[dk][0] * 1e-3) / 1e12 / peak, 4)},
+                             "traffic": (pmc_traffic(dk) or {}).get("bytes_per_launch"),
+                             "traffic_source": (pmc_traffic(dk) or {}).get("source"),
+                             "traffic_provenance": ("a COMMITTED constant, not measured by this run: HBM bytes per launch of this "
+                                                    "kernel from two separate rocprofv3 --pmc passes (FETCH_SIZE x 2 + WRITE_SIZE, "
+                                                    "--lanes 1) of `python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline "
+                                                    "--no-extras --no-verify --lanes 1`, tools/pmc_bench.sh -> "
+                                                    "tools/pmc_traffic_summary.py -> profiles/" +
+                                                    str((pmc_traffic(dk) or {}).get("source")) + " (file date " +
+                                                    str((pmc_traffic(dk) or {}).get("date")) + "); bench.py cannot run the profiler on itself"),
+                             "avg_launch_us": round(dms / dn * 1e3, 2),
+                             "flops_per_launch_avg": round(dfl / dn),
+                             **mfma_busy(dk, achieved, peak)},
+                "step_tflops": round(fwd_flops / ms_per_step / 1e9, 2),      # conv FLOPs / whole-step time (lanes overlap)
+                "conv_stack": {"ms": round(fwd_ms, 4), "tflops": round(fwd_flops / fwd_ms / 1e9, 2),
+                               "frac_of_mfma_peak": round(fwd_flops / fwd_ms / 1e9 / peak, 4),
+                               "gflop_per_image": round(fwd_flops / B / 1e9, 3)},
+                "decode": ({"mode": "fused into the head conv epilogue (no head tensor); NMS + limb parse kernel only",
+                            "ms": round(dec_ms, 4), "people": people} if fused else
+                           {"mode": "stand-alone: dense limb arg-max over the materialised head + NMS + limb parse",
+                            "ms": round(dec_ms, 4), "gbps": round(head_bytes / dec_ms / 1e6, 1),
+                            "frac_of_hbm_peak": round(head_bytes / dec_ms / 1e6 / 8000.0, 4), "people": people}),
+            })
+            if world == 1:
+                # PCIe-inclusive rate (NOT `value`): every step first copies the u8 frames from pinned host memory and
+                # ends with the compact decode result (counts, cells, boxes, scores) back on the host.
+                host = torch.from_numpy(prng.u8_frames(1234, B, (S, S))).pin_memory()
+                n = max(6, args.steps)
+                if pipe is not None:                 # untimed: every lane allocates its pinned read-back buffers once
+                    for r in [pipe.submit(host, to_host=True) for _ in range(max(1, args.lanes))]:
+                        r.ready.synchronize()
+                torch.cuda.synchronize(dev)
+                # the two copies alone (no compute queued): says whether a low PCIe-inclusive rate is the link / the NUMA
+                # placement of the pinned pages on this box, or the pipeline
+                h2d_dst = torch.empty_like(host, device=dev)
+                h2d_dst.copy_(host, non_blocking=True)
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    h2d_dst.copy_(host, non_blocking=True)
+                torch.cuda.synchronize(dev)
+                h2d_ms = (time.perf_counter() - t0) / 10 * 1e3
+                del h2d_dst
+                t1 = time.perf_counter()
+                if pipe is not None:
+                    # pinned frames -> the lane's own input buffer (H2D on the lane's stream) -> step -> the compact result
+                    # into the lane's pinned buffers (D2H behind the decode); the host unpacks batch i - lanes + 1 while the
+                    # later batches run: no synchronous copy anywhere
+                    pending = []
+                    host_s = [0.0, 0.0, 0.0]             # host seconds in submit / waiting on the ready event / unpack
+
+                    def collect(r):
+                        ta = time.perf_counter()
+                        r.ready.synchronize()
+                        tb = time.perf_counter()
+                        out = r.hosted.unpack()
+                        host_s[1] += tb - ta
+                        host_s[2] += time.perf_counter() - tb
+                        return out
+
+                    for it in range(n):
+                        ta = time.perf_counter()
+                        pending.append(pipe.submit(host, to_host=True))
+                        host_s[0] += time.perf_counter() - ta
+                        if len(pending) == max(1, args.lanes):
+                            hosted = collect(pending.pop(0))
+                    for r in pending:
+                        hosted = collect(r)
+                    pcie_people = sum(h["n"] for h in hosted)
+                else:
+                    for it in range(n):
+                        frames.copy_(host, non_blocking=True)
+                        hosted = step().to_host()
+                    pcie_people = sum(h["n"] for h in hosted)
+                torch.cuda.synchronize(dev)
+                dt1 = time.perf_counter() - t1
+                result["pcie_inclusive"] = {"value": round(B * n / dt1, 2), "unit": "images/sec",
+                                            "ms_per_step": round(dt1 / n * 1e3, 4), "h2d_bytes_per_step": host.numel(),
+                                            "host_ms_per_step": ({k: round(v / n * 1e3, 4) for k, v in
+                                                                  zip(("submit", "wait", "unpack"), host_s)}
+                                                                 if pipe is not None else None),
+                                            "h2d_alone_ms": round(h2d_ms, 4),
+                                            "h2d_alone_gbps": round(host.numel() / h2d_ms / 1e6, 2),
+                                            "people": int(pcie_people),
+                                            "slow_mode": bool(B * n / dt1 < 0.75 * value),
+                                            "slow_mode_note": "true = this process ran the PCIe loop in the slow mode seen on some boxes / processes "
+                                                              "(< 0.75 of `value` although h2d_alone_gbps is normal: host submit or GPU-side "
+                                                              "wait 2-3x the usual, profiles/r03/pcie_modes_sdma.txt); `value` is unaffected "
+                                                              "(frames resident in HBM)",
+                                            "note": "per step: H2D of the pinned u8 frames into the lane's input buffer, the "
+                                                    "step, D2H of the compact result (first 64 people slots per image) into pinned "
+                                                    "buffers, all queued on the lane's stream; the host unpacks a batch while the "
+                                                    "next ones run"}
+            if world == 1 and not args.no_extras:
+                if pipe is not None:
+                    pipe.close()
+                result.update(extra_sections(args, dev, net, frames, dec))
+            # what `value` is worth in the TASK metric, right beside it: the timed mode's people against the reference pipeline's
+            # (8 calibrated frames, the reference's own matcher; `ap_vs_reference` / `bf16_agreement` hold the details)
+            apv, agr = result.get("ap_vs_reference", {}), result.get("bf16_agreement", {})
+            if args.dtype == "bf16" and "bf16" in apv and "reproduced_exactly" in agr:
+                result["value_fidelity"] = {"total_ap": apv["bf16"][-1], "ap_ceiling": apv["self"][-1],
+                                            "reference_people_reproduced_exactly": f"{agr['reproduced_exactly']}/{agr['reference_people']}",
+                                            "same_root": f"{agr['same_root']}/{agr['reference_people']}",
+                                            "task_equivalent": bool(agr["reproduced_exactly"] >= 0.97 * agr["reference_people"]),
+                                            "modes_that_are": "float16x3 (`f16x3_mode`), float32 (`f32_parity_mode`): all people, AP = ceiling"}
+            if verified is not None:
+                if "bf16_agreement" in result or "reference_agreement" in result:
+                    ra = result.get("reference_agreement", result.get("bf16_agreement"))
+                    verified["reference_agreement"] = {k: ra[k] for k in ("reference_people", "reproduced_exactly", "same_root",
+                                                                          "same_root_frac", "keypoint_cell_agreement")
+                                                       if k in ra}
+                result["batch_consistency"] = verified
+            if world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline(args.arch, 4, S)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

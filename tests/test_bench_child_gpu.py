@@ -20,7 +20,7 @@ def _run(extra, env_extra=None, timeout=420, gpus=2):
     env.pop("OMP_NUM_THREADS", None)                            # bench.py's self-launch divides the cores itself
     env.update(env_extra or {})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--windows", "2",
-           "--no-extras", "--no-cpu-baseline"] + extra
+           "--full", "--no-extras", "--no-cpu-baseline"] + extra
     # own session: on a timeout the WHOLE group (bench.py, torch.distributed.run, the ranks) is killed, so that no rank is left
     # holding the GPU for the tests that follow; the timeout stays well below pytest's per-test limit (tools/gpu_round.sh: 900 s)
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, start_new_session=True)
@@ -108,7 +108,7 @@ def test_rccl_branch_runs_with_one_rank(workload):
     env.pop("PPN_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--windows", "2", "--no-extras", "--no-cpu-baseline", "--workload", workload]
+           "--windows", "2", "--full", "--no-extras", "--no-cpu-baseline", "--workload", workload]
     if workload == "train":
         cmd += ["--batch", "8"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420, cwd=ROOT)

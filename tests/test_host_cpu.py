@@ -352,3 +352,29 @@ def test_mfma_busy_constants_resolve_for_the_dominant_kernel():
     assert 0.3 < r["mfma_busy"] < 0.9 and 0.2 < r["mfma_busy_conv_stack"] < 0.9
     assert 1.5 < r["held_clock_ghz"] < 2.5 and abs(r["frac_of_held_clock_peak"] - 0.5 * 2.4 / r["held_clock_ghz"]) < 1e-3
     assert "tools/pmc_mfma.sh" in r["mfma_busy_provenance"]
+
+
+def test_bench_dump_outputs_fixed_shapes_and_dtypes(tmp_path):
+    """bench.py --dump-outputs: the people lists as fixed-shape float arrays (slots beyond an image's count filled), integer
+    fields exactly as float64, f32 kept; the total is capped."""
+    import torch
+    import bench
+    from pytorch_pose_proposal_network_amd.decode import DecodeResult
+    B, M, K, E = 3, 8, 18, 17
+    g = torch.Generator().manual_seed(0)
+    res = DecodeResult(torch.tensor([2, 0, 8], dtype=torch.int32),
+                       torch.randint(-1, 500, (B, M, K), dtype=torch.int32, generator=g),
+                       torch.randint(0, 400, (B, M, E), dtype=torch.int32, generator=g),
+                       torch.rand(B, M, K, 4, generator=g), torch.rand(B, M, K, generator=g), M)
+    bench.dump_outputs(str(tmp_path), bench.decode_arrays(res))
+    d = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert sorted(d) == ["bbox", "count", "kp_cell", "limb_arg", "score"]
+    assert d["count"].dtype == np.float64 and d["kp_cell"].dtype == np.float64 and d["bbox"].dtype == np.float32
+    assert d["count"].tolist() == [2, 0, 8]
+    for name, fill in (("kp_cell", -1), ("limb_arg", -1), ("bbox", 0), ("score", 0)):
+        src = getattr(res, name).numpy()
+        assert np.array_equal(d[name][0, :2], src[0, :2]) and (d[name][0, 2:] == fill).all(), name
+        assert (d[name][1] == fill).all() and np.array_equal(d[name][2], src[2]), name
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    assert not os.path.exists(tmp_path / "big")

@@ -4,8 +4,8 @@
 V=$1; R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/${2:-ab}; N=${3:-2}; mkdir -p $O; cd $R
 for i in $(seq 1 $N); do
   for on in 0 1; do
-    env $V=$on timeout -k 10 200 python3 bench.py --no-extras --no-cpu-baseline --no-verify --lanes 3 > $O/l3_${on}_$i.json 2>/dev/null
-    env $V=$on timeout -k 10 200 python3 bench.py --no-extras --no-cpu-baseline --no-verify --lanes 1 --layers > $O/l1_${on}_$i.json 2> $O/l1_${on}_$i.layers.txt
+    env $V=$on timeout -k 10 200 python3 bench.py --full --no-extras --no-cpu-baseline --no-verify --lanes 3 > $O/l3_${on}_$i.json 2>/dev/null
+    env $V=$on timeout -k 10 200 python3 bench.py --full --no-extras --no-cpu-baseline --no-verify --lanes 1 --layers > $O/l1_${on}_$i.json 2> $O/l1_${on}_$i.layers.txt
     python3 - <<PY
 import json
 for n in ("l3","l1"):

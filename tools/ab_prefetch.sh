@@ -3,8 +3,8 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/${1:-r05b}; mkdir -p $O; cd $R
 for i in 1 2; do
   for pf in 0 1; do
-    PPN_PREFETCH=$pf timeout -k 10 200 python3 bench.py --no-extras --no-cpu-baseline --no-verify --lanes 3 > $O/l3_pf${pf}_$i.json 2>/dev/null
-    PPN_PREFETCH=$pf timeout -k 10 200 python3 bench.py --no-extras --no-cpu-baseline --no-verify --lanes 1 --layers > $O/l1_pf${pf}_$i.json 2> $O/l1_pf${pf}_$i.layers.txt
+    PPN_PREFETCH=$pf timeout -k 10 200 python3 bench.py --full --no-extras --no-cpu-baseline --no-verify --lanes 3 > $O/l3_pf${pf}_$i.json 2>/dev/null
+    PPN_PREFETCH=$pf timeout -k 10 200 python3 bench.py --full --no-extras --no-cpu-baseline --no-verify --lanes 1 --layers > $O/l1_pf${pf}_$i.json 2> $O/l1_pf${pf}_$i.layers.txt
     python3 - <<PY
 import json
 for n in ("l3","l1"):

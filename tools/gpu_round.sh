@@ -13,8 +13,8 @@ for step in "$@"; do
     tests_all) timeout -k 10 1100 python3 -m pytest tests -q -m gpu -p no:cacheprovider --timeout 900 > $O/${T}_pytest.log 2>&1; rc=$?; tail -15 $O/${T}_pytest.log;;
     tests:*) timeout -k 10 1000 python3 -m pytest ${step#tests:} -q -m gpu -p no:cacheprovider --timeout 900 -s > $O/${T}_pytest_sel.log 2>&1; rc=$?; tail -25 $O/${T}_pytest_sel.log;;
     clock)  (timeout -k 10 120 python3 tools/clock_conv.py; timeout -k 10 120 python3 tools/clock_conv.py --f16) 2>&1 | grep -v amdgpu.ids > $O/${T}_clock.txt; rc=$?; cat $O/${T}_clock.txt;;
-    bench)  timeout -k 10 600 python3 bench.py --layers > $O/${T}_bench.json 2> $O/${T}_bench_layers.txt; rc=$?; head -c 1500 $O/${T}_bench.json; echo;;
-    benchlite) timeout -k 10 300 python3 bench.py --layers --no-extras --no-cpu-baseline > $O/${T}_benchlite.json 2> $O/${T}_benchlite_layers.txt; rc=$?; head -c 600 $O/${T}_benchlite.json; echo;;
+    bench)  timeout -k 10 600 python3 bench.py --full --layers > $O/${T}_bench.json 2> $O/${T}_bench_layers.txt; rc=$?; head -c 1500 $O/${T}_bench.json; echo;;
+    benchlite) timeout -k 10 300 python3 bench.py --full --layers --no-extras --no-cpu-baseline > $O/${T}_benchlite.json 2> $O/${T}_benchlite_layers.txt; rc=$?; head -c 600 $O/${T}_benchlite.json; echo;;
     *) echo "unknown step $step";;
   esac
   echo "step $step rc=$rc"

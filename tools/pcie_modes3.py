@@ -3,7 +3,7 @@ import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run(tag, env_extra=None):
     env = dict(os.environ, **(env_extra or {}))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extras", "--windows", "10"], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-extras", "--windows", "10"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
     for line in p.stdout.splitlines():
         if line.startswith("{"):
