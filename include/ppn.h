@@ -481,6 +481,12 @@ int ppn_plan_add_stem012(ppn_plan* p, int32_t src_is_u8, const void* src, int32_
  * type; PPN_STEM_IO(PPN_F16, PPN_BF16) = IEEE-half operands and on-chip tensors, bf16 OUTPUT tensors (what the bf16 mode runs
  * since round 4: the stem's rounding noise is amplified by every layer behind it, csrc/stem012.hip). */
 #define PPN_STEM_IO(internal, out) ((internal) | (((out) + 1) << 8))
+/* PPN_STEM_IO(PPN_F16X3, PPN_F32): the stem for the exact modes (csrc/stem012_x3.hip) -- split-f16 internals with the error
+ * model of a PPN_F16X3 convolution (activations and weights as half pairs hi = half(v), lo' = half((v - hi) * 2^11), weights
+ * scaled by a power of two per layer, a_hi w_hi + a_hi w_lo + a_lo w_hi on f16 MFMAs with f32 accumulation, BN and ReLU in
+ * f32; u8 frames keep the exact integer input), outputs NHWC f32 [B, (H+1)/2, (W+1)/2, 32] like the three PPN_F32
+ * launches it replaces, within 1.2e-5 of the output scale of them.  Not combinable with PPN_STEM_RAW_S2; the layer-by-layer
+ * entry points (ppn_stem7x7, ppn_stem01) reject it. */
 /* PPN_STEM_RAW_S2 (or-ed into the dtype of the *_dt entry points; round 5): out_raw receives only the pixels with even row AND
  * column, as NHWC [batch, (Ho + 1) / 2, (Wo + 1) / 2, 32] -- when the raw stem output's only reader is the first BasicBlock's
  * 1x1 stride-2 projection (drn.py:53-54, 176-181), which reads exactly those pixels: 19 instead of 75 MB written at batch 32,

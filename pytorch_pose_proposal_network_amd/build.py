@@ -37,6 +37,7 @@ SOURCES = [
     ("stem3x3.hip", NOSLP),
     ("stem01.hip", NOSLP),
     ("stem012.hip", NOSLP),
+    ("stem012_x3.hip", NOSLP),
     ("plan.hip", []),
     ("loss.hip", []),
     ("train.hip", []),

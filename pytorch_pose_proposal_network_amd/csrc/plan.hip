@@ -96,7 +96,7 @@ static int run_op(ppn_plan::Op& op, hipStream_t st) {
         return rc;
     }
     if (op.kind == 4) {
-        if (op.kname.empty()) op.kname = "stem012_kernel";
+        if (op.kname.empty()) op.kname = op.dtype == PPN_STEM_IO(PPN_F16X3, PPN_F32) ? "stem012_x3_kernel" : "stem012_kernel";
         return ppn::stem012_launch(op.dtype, op.src_is_u8, op.src, op.batch, op.h, op.w, op.weight, op.scale, op.shift, op.mean,
                                    op.stdv, op.w1, op.scale1, op.shift1, op.w2, op.scale2, op.shift2, op.scale3,
                                    op.shift3, op.out, op.out2, st);
@@ -196,8 +196,9 @@ extern "C" int ppn_plan_add_stem012_dt(ppn_plan* p, int32_t dtype, int32_t src_i
                                     const float* shift1, const float* w2, const float* scale2, const float* shift2,
                                     const float* scale3, const float* shift3, void* out_raw, void* out_act) {
     if (!p) return ppn::fail(PPN_E_INVALID, "ppn_plan_add_stem012: NULL plan");
-    if ((dtype & 0xff) != PPN_BF16 && (dtype & 0xff) != PPN_F16)
-        return ppn::fail(PPN_E_INVALID, "ppn_plan_add_stem012: dtype must be PPN_BF16, PPN_F16 or PPN_STEM_IO(PPN_F16, PPN_BF16)");
+    if ((dtype & 0xff) != PPN_BF16 && (dtype & 0xff) != PPN_F16 && dtype != PPN_STEM_IO(PPN_F16X3, PPN_F32))
+        return ppn::fail(PPN_E_INVALID, "ppn_plan_add_stem012: dtype must be PPN_BF16, PPN_F16, PPN_STEM_IO(PPN_F16, PPN_BF16) "
+                         "or PPN_STEM_IO(PPN_F16X3, PPN_F32)");
     ppn_plan::Op op{};
     op.kind = 4;
     op.dtype = dtype; op.src_is_u8 = src_is_u8; op.src = src; op.batch = batch; op.h = h; op.w = w;

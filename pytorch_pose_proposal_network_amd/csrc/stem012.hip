@@ -603,6 +603,11 @@ __global__ void __launch_bounds__(256, 2) stem012_kernel(Stem012Args a) {
 }  // namespace
 
 namespace ppn {
+int stem012_x3_launch(int src_is_u8, const void* src, int batch, int h, int w, const float* w0, const float* s0,
+                      const float* b0, const float* mean, const float* stdv, const float* w1, const float* s1,
+                      const float* b1, const float* w2, const float* s2, const float* b2, const float* s3, const float* b3,
+                      void* out_raw, void* out_act, hipStream_t st);
+
 template <bool U8, typename H, typename HO = H>
 static int stem012_launch_T(const Stem012Args& a, unsigned grid, hipStream_t st) {
     static int max_lds_set = 0;
@@ -620,6 +625,9 @@ int stem012_launch(int dtype, int src_is_u8, const void* src, int batch, int h, 
         h < 1 || w < 1 || (s3 == nullptr) != (b3 == nullptr))
         return fail(PPN_E_INVALID, "ppn_stem012: bad arguments");
     if (src_is_u8 && (!mean || !stdv)) return fail(PPN_E_INVALID, "ppn_stem012: mean/std required for u8 input");
+    if (dtype == PPN_STEM_IO(PPN_F16X3, PPN_F32))       // split-f16 internals, f32 outputs (csrc/stem012_x3.hip)
+        return stem012_x3_launch(src_is_u8, src, batch, h, w, w0, s0, b0, mean, stdv, w1, s1, b1, w2, s2, b2, s3, b3, out_raw,
+                                 out_act, st);
     Stem012Args a;
     a.src = src; a.w0 = w0; a.s0 = s0; a.b0 = b0; a.w1 = w1; a.s1 = s1; a.b1 = b1; a.w2 = w2; a.s2 = s2; a.b2 = b2;
     a.s3 = s3; a.b3 = b3; a.out_raw = out_raw; a.out_act = out_act;
@@ -636,7 +644,8 @@ int stem012_launch(int dtype, int src_is_u8, const void* src, int batch, int h, 
     const int din = dtype & 0xff, dout = ((dtype >> 8) & 0xff) ? ((dtype >> 8) & 0xff) - 1 : din;
     a.raw_s2 = (dtype & PPN_STEM_RAW_S2) ? 1 : 0;
     if ((din != PPN_BF16 && din != PPN_F16) || (dout != PPN_BF16 && dout != PPN_F16) || (din == PPN_BF16 && dout != PPN_BF16))
-        return fail(PPN_E_INVALID, "ppn_stem012: dtype must be PPN_BF16, PPN_F16 or PPN_STEM_IO(PPN_F16, PPN_BF16)");
+        return fail(PPN_E_INVALID, "ppn_stem012: dtype must be PPN_BF16, PPN_F16, PPN_STEM_IO(PPN_F16, PPN_BF16) or "
+                    "PPN_STEM_IO(PPN_F16X3, PPN_F32)");
     int rc;
     if (din == PPN_F16 && dout == PPN_BF16)
         rc = src_is_u8 ? stem012_launch_T<true, _Float16, __bf16>(a, grid, st) : stem012_launch_T<false, _Float16, __bf16>(a, grid, st);

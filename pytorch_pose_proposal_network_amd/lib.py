@@ -16,6 +16,14 @@ PPN_ACT_NONE, PPN_ACT_RELU, PPN_ACT_LRELU, PPN_ACT_SIGMOID = 0, 1, 2, 3
 PPN_STEM_RAW_S2 = 1 << 16           # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
 
 
+def PPN_STEM_IO(internal: int, out: int) -> int:
+    """ppn_*stem012_dt dtype: the stem's internal type with a different output storage type (include/ppn.h)."""
+    return internal | ((out + 1) << 8)
+
+
+PPN_STEM_X3_F32 = PPN_STEM_IO(PPN_F16X3, PPN_F32)   # split-f16 fused stem, f32 outputs (csrc/stem012_x3.hip)
+
+
 class DecodeCfg(C.Structure):
     _fields_ = [
         ("K", C.c_int32), ("E", C.c_int32), ("sH", C.c_int32), ("sW", C.c_int32),

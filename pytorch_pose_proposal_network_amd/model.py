@@ -118,9 +118,12 @@ class PoseProposalNet:
             raise ValueError("exact_prefix is an option of the float16 mode and covers at least backbone.0 .. backbone.3")
         self._exact_names = tuple(f"backbone.{i}." for i in range(self.exact_prefix + 1)) if self.exact_prefix >= 3 else ()
         if self._exact_names:
-            if fuse_stem not in (None, False, True):
-                raise ValueError("an exact prefix runs the stem as f32 launches (fuse_stem False / True)")
-            fuse_stem = bool(fuse_stem)
+            # the stem as f32 launches (fuse_stem False / True), or as ONE split-f16 launch (fuse_stem="all":
+            # csrc/stem012_x3.hip, the float16x3 convolutions' error model, f32 outputs)
+            if fuse_stem not in (None, False, True, "all"):
+                raise ValueError("an exact prefix runs the stem as f32 launches (fuse_stem False / True) or as the "
+                                 "split-f16 fused stem (fuse_stem='all')")
+            fuse_stem = "all" if fuse_stem == "all" else bool(fuse_stem)
             if fuse_shortcut is None:
                 fuse_shortcut = os.environ.get("PPN_FUSE_SHORTCUT", "1") != "0"
             if fuse_shortcut and not callable(fuse_shortcut):
@@ -133,12 +136,14 @@ class PoseProposalNet:
                 self.compute_dtype == L.PPN_BF16 and os.environ.get("PPN_FUSE_STEM", "1") != "0")) else False
         if self.compute_dtype == L.PPN_F16X3:
             # split-f16 mode: the layers with cin < 64 (stem, first block's stride-2 convs) run as exact f32, launch by
-            # launch; the split kernel has no fused-shortcut instantiation
-            if fuse_stem or fuse_shortcut:
-                raise ValueError("the float16x3 mode runs the stem layer by layer and without fused shortcuts")
-            fuse_stem, fuse_shortcut = False, False
-        if fuse_stem == "all" and self.compute_dtype in (L.PPN_F32, L.PPN_F16X3):
-            raise ValueError("fuse_stem='all' (csrc/stem012.hip) is a 16-bit-mode kernel")
+            # launch -- or, with fuse_stem="all", the stem as one split-f16 launch (csrc/stem012_x3.hip); the split kernel
+            # has no fused-shortcut instantiation
+            if (fuse_stem and fuse_stem != "all") or fuse_shortcut:
+                raise ValueError("the float16x3 mode runs the stem layer by layer (or fused: fuse_stem='all') and without "
+                                 "fused shortcuts")
+            fuse_stem, fuse_shortcut = ("all" if fuse_stem == "all" else False), False
+        if fuse_stem == "all" and self.compute_dtype == L.PPN_F32:
+            raise ValueError("fuse_stem='all' (csrc/stem012.hip) is a 16-bit-mode kernel; the float32 mode stays exact f32")
         if self.compute_dtype == L.PPN_F16 and fuse_stem != "all" and not self._exact_names:
             raise ValueError("the float16 mode runs the stem through csrc/stem012.hip only (fuse_stem='all')")
         if fuse_stem != "all":                                # the half prefix starts with the fused stem's half outputs
@@ -350,7 +355,14 @@ class PoseProposalNet:
         exact = self.compute_dtype == L.PPN_F16X3 or (self._exact_names and op.name.startswith(self._exact_names))
         if not exact:
             return self.compute_dtype
+        if op.k == 7 and op.next_s2 is not None:      # fuse_stem="all": the split-f16 stem (f32 outputs, _is_x3_stem)
+            return L.PPN_F16X3
         return L.PPN_F16X3 if (op.k != 7 and op.cin % 64 == 0 and op.cout >= 64) else L.PPN_F32
+
+    def _is_x3_stem(self, op) -> bool:
+        """The fused stem of an exact mode (fuse_stem="all" with float16x3 or an exact prefix): one split-f16 launch
+        (csrc/stem012_x3.hip) that runs as PPN_F16X3 but STORES f32, like the three exact-f32 launches it replaces."""
+        return op.k == 7 and op.next_s2 is not None and self._op_dtype(op) == L.PPN_F16X3
 
     def _block64_pair(self, oi: int, store_dt) -> bool:
         """Do ops oi, oi + 1 form a 64-channel stride-1 BasicBlock that csrc/block64.hip runs as one launch?  (16-bit modes;
@@ -432,7 +444,7 @@ class PoseProposalNet:
         for op in self._ops:
             for name in (op.out_raw, op.out_act):
                 if name:
-                    producer[name] = self._op_dtype(op)
+                    producer[name] = L.PPN_F32 if self._is_x3_stem(op) else self._op_dtype(op)
         readers: Dict[str, set] = {}                  # tensor name -> dtypes of the launches that read it
         for op in self._ops:
             for name in (op.src, op.residual, op.ds_src):
@@ -573,11 +585,15 @@ class PoseProposalNet:
                 L.check(lib.ppn_plan_add_block(handle, C.byref(bd)), f"ppn_plan_add_block({op.name})")
                 continue
             if op.k == 7 and op.next_s2 is not None:
-                assert op.src == "input" and self.compute_dtype in (L.PPN_BF16, L.PPN_F16)
+                assert op.src == "input" and self.compute_dtype in (L.PPN_BF16, L.PPN_F16, L.PPN_F16X3)
                 out_dt = store_dt[op.out_raw or op.out_act]
-                sdt = self.stem_dtype if self.stem_dtype is not None else self.compute_dtype
-                if sdt != out_dt:
-                    sdt = sdt | ((out_dt + 1) << 8)                                  # PPN_STEM_IO(internal, out)
+                if self._is_x3_stem(op):                      # exact modes: split-f16 internals, f32 outputs
+                    assert out_dt == L.PPN_F32 and s2_tensor is None
+                    sdt = L.PPN_STEM_X3_F32
+                else:
+                    sdt = self.stem_dtype if self.stem_dtype is not None else self.compute_dtype
+                    if sdt != out_dt:
+                        sdt = sdt | ((out_dt + 1) << 8)                              # PPN_STEM_IO(internal, out)
                 if s2_tensor is not None:
                     sdt = sdt | L.PPN_STEM_RAW_S2
                 L.check(lib.ppn_plan_add_stem012_dt(handle, sdt, 1 if src_is_u8 else 0, src.data_ptr(), batch, h, w,
@@ -590,6 +606,7 @@ class PoseProposalNet:
                                                  bufs[op.out_raw].data_ptr() if op.out_raw else None,
                                                  bufs[op.out_act].data_ptr() if op.out_act else None),
                         "ppn_plan_add_stem012_dt")
+                add_splits(op)
                 continue
             if op.k == 7 and op.next3x3 is not None:
                 assert op.src == "input" and op.out_act is None
