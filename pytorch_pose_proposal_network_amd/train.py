@@ -40,24 +40,42 @@ def _f32(t: torch.Tensor, n: int, name: str) -> int:
 _ws_cache = {}
 
 
-def _workspace(channels: int, device, nstreams: int = 1) -> torch.Tensor:
+class _Workspace:
+    """One BatchNorm workspace (the partial sums of a reduction) and the generation of its contents.  EVERY call that lets a
+    kernel write the buffer -- bn_train_forward, bn_train_backward, conv2d_nhwc(..., stats=), colsum -- calls written()
+    before its launch; a ConvStats is valid only at the generation it was made at (_stats_blocks)."""
+    __slots__ = ("buf", "gen")
+
+    def __init__(self, buf):
+        self.buf, self.gen = buf, 0
+
+    def data_ptr(self) -> int:
+        return self.buf.data_ptr()
+
+    def written(self):
+        self.gen += 1
+
+
+def _workspace(channels: int, device, nstreams: int = 1) -> _Workspace:
     key = (channels, str(device), torch.cuda.current_stream(device).cuda_stream, nstreams)   # one per stream (partial sums)
     ws = _ws_cache.get(key)
     if ws is None:
-        ws = torch.empty(nstreams * L.load().ppn_bn_workspace_bytes(channels), dtype=torch.uint8, device=device)
-        _ws_cache[key] = ws
+        ws = _ws_cache[key] = _Workspace(torch.empty(nstreams * L.load().ppn_bn_workspace_bytes(channels), dtype=torch.uint8,
+                                                     device=device))
     return ws
 
 
 class ConvStats:
     """BatchNorm partial sums a convolution's epilogue left in the BatchNorm workspace of its stream (ppn_conv_desc.stats_mode):
     `blocks` pixel tiles (0: the launch had no such epilogue -- the BatchNorm call then runs its own reduction pass), in the
-    workspace tensor `ws`.  Hand it to the bn_train_forward / bn_train_backward call that FOLLOWS the convolution on the same
-    stream, with no other BatchNorm of that channel count in between (they share the workspace)."""
-    __slots__ = ("ws", "blocks", "mode", "tensor")
+    workspace `ws`.  Hand it to the bn_train_forward / bn_train_backward call that FOLLOWS the convolution on the same stream.
+    Generation rule: it records the workspace's generation when it is made (right after the launch that wrote the sums) and is
+    refused (ValueError) once any other writer of that workspace has advanced it -- the sums it describes are gone."""
+    __slots__ = ("ws", "blocks", "mode", "tensor", "gen")
 
     def __init__(self, ws, blocks, mode, tensor):
         self.ws, self.blocks, self.mode, self.tensor = ws, blocks, mode, tensor
+        self.gen = ws.gen if ws is not None else None
 
 
 _FUSE_STATS = os.environ.get("PPN_TRAIN_FUSE_STATS", "1") != "0"      # A/B switch of the trainer's use of ConvStats
@@ -69,6 +87,8 @@ def _stats_blocks(stats, ws, mode: int, tensor: torch.Tensor) -> int:
         return 0
     if stats.mode != mode or stats.ws is not ws or stats.tensor.data_ptr() != tensor.data_ptr():
         raise ValueError("ConvStats belongs to another tensor / workspace / pass")
+    if stats.gen != ws.gen:                  # a caller's ordering error: raise, a fallback would hide the lost fusion as a slowdown
+        raise ValueError("ConvStats is stale: another launch has overwritten the BatchNorm workspace since (ConvStats.gen)")
     return stats.blocks
 
 
@@ -116,6 +136,7 @@ def bn_train_forward(x: torch.Tensor, gamma, beta, running_mean=None, running_va
             raise ValueError("bn_train_forward: emit_stats needs the output")
         blocks = C.c_int32(0)
         d.emit_blocks = C.pointer(blocks)
+    ws.written()
     L.check(lib.ppn_bn_train_fwd(C.byref(d), L.current_stream_ptr()), "ppn_bn_train_fwd")
     if emit_stats:
         return y, saved, ConvStats(ws, blocks.value, 1, y)
@@ -169,8 +190,10 @@ def bn_train_backward(x: torch.Tensor, dy: torch.Tensor, gamma, beta, saved: BnS
         d.next_x, d.next_act, d.next_blocks = x2.data_ptr(), ACT[act2], C.pointer(nblocks)
         d.next_gamma, d.next_beta = _f32(gamma2, c, "gamma2"), _f32(beta2, c, "beta2")
         d.next_mean, d.next_rstd = saved2.mean.data_ptr(), saved2.rstd.data_ptr()
+        ws.written()
         L.check(lib.ppn_bn_train_bwd(C.byref(d), L.current_stream_ptr()), "ppn_bn_train_bwd")
         return dx, dgamma, dbeta, ConvStats(ws, nblocks.value, 2, dx)
+    ws.written()
     if nstreams == 1:
         L.check(lib.ppn_bn_train_bwd(C.byref(d), L.current_stream_ptr()), "ppn_bn_train_bwd")
     else:
@@ -235,6 +258,29 @@ def probe_stats(g4, total: torch.Tensor, coeff):
                                               total.data_ptr(), cf, n, gw4.data_ptr(), st.data_ptr(), ws.data_ptr(),
                                               L.current_stream_ptr()), "ppn_gradnorm_probe_stats")
     return gw4, st
+
+
+def limb_remainder_trusted(coeff, compute_dtype: int, n_rest: Optional[float] = None, n_tot: Optional[float] = None) -> bool:
+    """May the limb loss's probe gradient be taken as the remainder (sum_i coeff_i dL_i/dW - sum_{i<4} coeff_i dL_i/dW) / coeff_4
+    instead of a direct fifth pass?  Not when coeff_4 is too small to divide by, and not -- 16-bit modes, where the total and the
+    unary probes come from differently rounded passes (relative noise ~2^-8 each) -- when the remainder is not clearly above
+    the rounding noise of the total.  n_rest, n_tot: ||unscaled remainder||^2 and ||total||^2 (None: not known yet, the
+    coefficient test alone)."""
+    if not coeff[4] > 1e-3 * max(coeff):
+        return False
+    if compute_dtype == L.PPN_F32 or n_rest is None:
+        return True
+    return n_rest > (16.0 * 2.0 ** -8) ** 2 * n_tot
+
+
+def colsum(x: torch.Tensor, out: torch.Tensor, device=None):
+    """out f32[C] = the sum of x [..., C] over everything but its last dimension (a bias gradient).  Its partial sums go through
+    the BatchNorm workspace of (C, device, stream) -- device: as the caller names it (the workspaces are keyed by that name)."""
+    c = x.shape[-1]
+    ws = _workspace(c, x.device if device is None else device)
+    ws.written()
+    L.check(L.load().ppn_colsum(_dtype_code(x), x.data_ptr(), x.numel() // c, c, _f32(out, c, "out"), ws.data_ptr(),
+                                L.current_stream_ptr()), "ppn_colsum")
 
 
 def allreduce_mean_(flat: torch.Tensor, group=None) -> float:
@@ -428,6 +474,7 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, stride: int = 1, dilation: int
         d.stats_mode, d.stats_act, d.stats_x = 2, ACT[bact], bx.data_ptr()
         d.stats_gamma, d.stats_beta = _f32(gamma, cout, "gamma"), _f32(beta, cout, "beta")
         d.stats_mean, d.stats_rstd = saved.mean.data_ptr(), saved.rstd.data_ptr()
+    ws.written()
     L.check(lib.ppn_conv2d_fused(C.byref(d), st), "ppn_conv2d_fused")
     return out, ConvStats(ws, tiles.value, d.stats_mode, out)
 
@@ -517,7 +564,6 @@ def repack_all(device, storages=None) -> int:
     return len(keys)
 
 
-
 def _zero_page(device) -> torch.Tensor:
     z = _zero_pages.get(str(device))
     if z is None:
@@ -570,9 +616,8 @@ def upsample_zero(src: torch.Tensor, stride: int, dst_h: int, dst_w: int) -> tor
     return dst
 
 
-import os as _os
-_S2_PARITY = _os.environ.get("PPN_DGRAD_S2_PARITY", "1") != "0"
-_S2_STACKED = _os.environ.get("PPN_DGRAD_S2_STACKED", "1") != "0"
+_S2_PARITY = os.environ.get("PPN_DGRAD_S2_PARITY", "1") != "0"
+_S2_STACKED = os.environ.get("PPN_DGRAD_S2_STACKED", "1") != "0"
 _S2_IDX = {}
 
 
@@ -669,7 +714,6 @@ def _wgrad_ws(nbytes: int, device) -> torch.Tensor:
 
 
 def _force_dp() -> bool:
-    import os
     return os.environ.get("PPN_FORCE_DP", "0") == "1"
 
 

@@ -25,6 +25,7 @@ that tail per loss, whose adjoints join the first-order ones before the backbone
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import numpy as np
@@ -37,6 +38,175 @@ from . import train as T
 from .loss import PPNLoss
 
 _BUFFER_SUFFIXES = (".running_mean", ".running_var", ".num_batches_tracked")
+
+
+# ---- the units of arch._units: one class per kind ------------------------------------------------------------------------
+# A training pass makes one object per unit; the list of them is the tape.  forward(tr, x, st, emit) -> (output, ConvStats or
+# None) saves what the backward needs as attributes; st: the BatchNorm sums of x where the unit opens with a BatchNorm over it,
+# emit: the unit above does (it wants the sums of the output).  backward(tr, g, gst, below_bn, so) -> (input gradient, ConvStats
+# or None); gst: the sums of g for entry_bn(), below_bn: the entry_bn() of the unit below, whose dy the input gradient is.
+# Statistics travel only where the 16-bit mode fuses them (PPNTrainer._fuse_stats); `tr` is the trainer (parameters, helpers).
+class _Unit:
+    opens_with_bn = False                 # forward() starts with a BatchNorm over the unit's input
+    FIRST = "{u.prefix}.conv1.weight"     # the unit's first parameter in the flat buffer (its parameters are contiguous)
+
+    def __init__(self, u: A.Unit):
+        self.u, self.first = u, self.FIRST.format(u=u)
+
+    def entry_bn(self):
+        """(x, prefix, act, saved) of the BatchNorm that takes the unit's OUTPUT gradient as its dy, from the unit's own tape"""
+        return None
+
+
+class _Cbr(_Unit):
+    """conv - BatchNorm - ReLU (drn.py:123-128, 192-202)"""
+    FIRST = "{u.prefix}.{u.conv_idx}.weight"
+
+    def __init__(self, u):
+        super().__init__(u)
+        self.bnp = f"{u.prefix}.{u.conv_idx + 1}"
+
+    def forward(self, tr, x, st, emit):
+        u = self.u
+        if u.k == 7:          # the stem reads the NCHW f32 image; self.x (the NHWC copy for its weight gradient): PPNTrainer.forward
+            B, _, H, W = x.shape
+            self.y = torch.empty(B, H, W, u.cout, dtype=tr.tdt, device=tr.device)
+            L.check(L.load().ppn_stem7x7(tr.compute_dtype, 0, x.data_ptr(), B, H, W, tr.P[self.first].data_ptr(), None,
+                                         None, None, None, self.y.data_ptr(), L.current_stream_ptr()), "ppn_stem7x7")
+            yst = None
+        else:
+            self.x = x
+            self.y, yst = tr._conv_bn(x, self.first, u.stride, u.dil[0], u.dil[0])
+        z, self.saved, zst = tr._bn(self.y, self.bnp, "relu", stats=yst, emit=emit)
+        return z, zst
+
+    def entry_bn(self):
+        return self.y, self.bnp, "relu", self.saved
+
+    def backward(self, tr, g, gst, below_bn, so=None):
+        u, wn, d = self.u, self.first, self.u.dil[0]
+        dy, _ = tr._bn_bwd(self.y, g, self.bnp, "relu", self.saved, stats=gst)
+        if u.k == 7:
+            def wg0(x8=self.x, dy=dy, wn=wn):
+                dw8 = T.conv_wgrad(x8, dy, 7, 1, 1, 3)            # [16, 4 | 8, 7, 7]; input channels 3.. are zero
+                tr.G[wn].copy_(dw8[:, :3])
+            # the LAST weight gradient of the pass: on the main stream (idle from here on) beside the side stream's
+            # layer1 / layer2 weight gradients instead of behind them (PPN_TRAIN_WG0_MAIN=0: on the side stream)
+            if tr._wg0_main:
+                wg0()
+            else:
+                tr._on_side(wg0, self.x, dy)
+            return None, None                                      # the input needs no gradient
+        tr._wgrad(wn, self.x, dy, 3, u.stride, d, d)
+        return tr._dgrad_bn(dy, wn, self.x.shape[1:3], u.stride, d, d, below_bn)
+
+
+class _Basic(_Unit):
+    """pre-activation BasicBlock (drn.py:25-57, model.py:14-48)"""
+    opens_with_bn = True
+
+    def forward(self, tr, x, st, emit):
+        u, p = self.u, self.u.prefix
+        self.x = x
+        self.a, self.s1, _ = tr._bn(x, p + ".bn1", "relu", stats=st)
+        self.c1, c1st = tr._conv_bn(self.a, p + ".conv1.weight", u.stride, u.dil[0], u.dil[0])
+        self.b, self.s2, _ = tr._bn(self.c1, p + ".bn2", "relu", stats=c1st)
+        if u.downsample:
+            self.dsy, dst = tr._conv_bn(x, p + ".downsample.0.weight", u.stride, 1, 0)
+            r, self.s3, _ = tr._bn(self.dsy, p + ".downsample.1", "none", stats=dst)
+        else:
+            r = x
+        return T.conv2d_nhwc(self.b, tr.P[p + ".conv2.weight"], 1, u.dil[1], u.dil[1], add=r), None
+
+    def entry_bn(self):
+        return (self.dsy, self.u.prefix + ".downsample.1", "none", self.s3) if self.u.downsample else None
+
+    def backward(self, tr, g, gst, below_bn, so=None):
+        u, p = self.u, self.u.prefix
+        hw = self.x.shape[1:3]
+        if u.downsample:
+            # first: its BatchNorm (entry_bn) takes the sums the unit above folded while it wrote g, and every BatchNorm /
+            # statistics epilogue of this channel count on this stream overwrites them (train.ConvStats: refused when stale)
+            dds, _ = tr._bn_bwd(self.dsy, g, p + ".downsample.1", "none", self.s3, stats=gst)
+            tr._wgrad(p + ".downsample.0.weight", self.x, dds, 1, u.stride, 1, 0)
+            dxr = T.conv_dgrad(dds, tr.P[p + ".downsample.0.weight"], hw, u.stride, 1, 0)
+        else:
+            dxr = g
+        tr._wgrad(p + ".conv2.weight", self.b, g, 3, 1, u.dil[1], u.dil[1])
+        db, dbst = tr._dgrad_bn(g, p + ".conv2.weight", self.b.shape[1:3], 1, u.dil[1], u.dil[1],
+                                (self.c1, p + ".bn2", "relu", self.s2))
+        dc1, _ = tr._bn_bwd(self.c1, db, p + ".bn2", "relu", self.s2, stats=dbst)
+        tr._wgrad(p + ".conv1.weight", self.a, dc1, 3, u.stride, u.dil[0], u.dil[0])
+        da, dast = tr._dgrad_bn(dc1, p + ".conv1.weight", hw, u.stride, u.dil[0], u.dil[0], (self.x, p + ".bn1", "relu", self.s1))
+        return tr._bn_bwd(self.x, da, p + ".bn1", "relu", self.s1, dx_add=dxr, stats=dast, next_bn=below_bn)
+
+
+class _Bottleneck(_Unit):
+    """post-activation Bottleneck (drn.py:77-97)"""
+
+    def forward(self, tr, x, st, emit):
+        u, p = self.u, self.u.prefix
+        self.x = x
+        self.y1, st1 = tr._conv_bn(x, p + ".conv1.weight")
+        self.h1, self.s1, _ = tr._bn(self.y1, p + ".bn1", "relu", stats=st1)
+        self.y2, st2 = tr._conv_bn(self.h1, p + ".conv2.weight", u.stride, u.dil[1], u.dil[1])
+        self.h2, self.s2, _ = tr._bn(self.y2, p + ".bn2", "relu", stats=st2)
+        self.y3, st3 = tr._conv_bn(self.h2, p + ".conv3.weight")
+        z3, self.s3, _ = tr._bn(self.y3, p + ".bn3", "none", stats=st3)
+        if u.downsample:
+            self.yd, std = tr._conv_bn(x, p + ".downsample.0.weight", u.stride, 1, 0)
+            r, self.sd, _ = tr._bn(self.yd, p + ".downsample.1", "none", stats=std)
+        else:
+            r = x
+        self.out = T.add_relu(z3, r)
+        return self.out, None
+
+    def backward(self, tr, g, gst, below_bn, so=None):
+        u, p = self.u, self.u.prefix
+        hw = self.x.shape[1:3]
+        dsum = T.relu_mask(self.out, g)                              # through relu(z3 + r)
+        dy3, _ = tr._bn_bwd(self.y3, dsum, p + ".bn3", "none", self.s3)
+        tr._wgrad(p + ".conv3.weight", self.h2, dy3, 1)
+        dh2, dh2st = tr._dgrad_bn(dy3, p + ".conv3.weight", self.h2.shape[1:3], 1, 1, 0, (self.y2, p + ".bn2", "relu", self.s2))
+        dy2, _ = tr._bn_bwd(self.y2, dh2, p + ".bn2", "relu", self.s2, stats=dh2st)
+        tr._wgrad(p + ".conv2.weight", self.h1, dy2, 3, u.stride, u.dil[1], u.dil[1])
+        dh1, dh1st = tr._dgrad_bn(dy2, p + ".conv2.weight", self.h1.shape[1:3], u.stride, u.dil[1], u.dil[1],
+                                  (self.y1, p + ".bn1", "relu", self.s1))
+        dy1, _ = tr._bn_bwd(self.y1, dh1, p + ".bn1", "relu", self.s1, stats=dh1st)
+        tr._wgrad(p + ".conv1.weight", self.x, dy1, 1)
+        if u.downsample:
+            dyd, _ = tr._bn_bwd(self.yd, dsum, p + ".downsample.1", "none", self.sd)
+            tr._wgrad(p + ".downsample.0.weight", self.x, dyd, 1, u.stride, 1, 0)
+            dxr = T.conv_dgrad(dyd, tr.P[p + ".downsample.0.weight"], hw, u.stride, 1, 0)
+        else:
+            dxr = dsum
+        return T.conv_dgrad(dy1, tr.P[p + ".conv1.weight"], hw, add=dxr), None
+
+
+class _Head(_Unit):
+    """PPN head, model.py:113-136; its backward is PPNTrainer._head_backward (shared with the GradNorm probe passes)"""
+    opens_with_bn = True
+    FIRST = "conv1x1_1.weight"
+
+    def forward(self, tr, x, st, emit):
+        P = tr.P
+        self.R = x
+        self.h0, self.s0, _ = tr._bn(x, "bn0_1", "lrelu", stats=st)
+        self.a1, a1st = tr._conv_bn(self.h0, "conv1x1_1.weight")
+        self.h1, self.s1, _ = tr._bn(self.a1, "bn1", "lrelu", stats=a1st)
+        self.a2, a2st = tr._conv_bn(self.h1, "conv1.weight", 1, 1, 1)
+        self.h2, self.s2, _ = tr._bn(self.a2, "bn0_2", "lrelu", stats=a2st)
+        self.a3 = T.conv2d_nhwc(self.h2, P["conv1x1_2.weight"], add=x)
+        self.c2, c2st = tr._conv_bn(self.a3, "conv2.weight", 1, 1, 1, bias=P["conv2.bias"])
+        self.h3, self.s3, _ = tr._bn(self.c2, "bn2", "lrelu", stats=c2st)
+        self.head = T.conv2d_nhwc(self.h3, P["conv3.weight"], bias=P["conv3.bias"], act=L.PPN_ACT_SIGMOID, nchw_f32=True)
+        return self.head, None
+
+    def backward(self, tr, g, gst, below_bn, so=None):
+        return tr._head_backward(self, g, probe_only=False, so=so, next_bn=below_bn)
+
+
+_UNIT_KINDS = {"cbr": _Cbr, "basic": _Basic, "bottleneck": _Bottleneck, "head": _Head}
 
 
 class PPNTrainer:
@@ -89,7 +259,6 @@ class PPNTrainer:
         self.criterion = PPNLoss(insize=insize, outsize=(insize[0] // 16, insize[1] // 16))
         self.base: Optional[torch.Tensor] = None
         self._tape = None
-        import os
         self._side = (torch.cuda.Stream(device=self.device)
                       if os.environ.get("PPN_TRAIN_SIDE_STREAM", "1") != "0" else None)
         # (A high-priority probe stream was tried -- PPN_TRAIN_PROBE_PRIORITY=-1 -- because the main stream waits ~0.65 ms
@@ -229,42 +398,44 @@ class PPNTrainer:
         return self.opt.lr
 
     # ---- small helpers ------------------------------------------------------------------------------------------
+    # BatchNorm statistics from the neighbouring launch (train.ConvStats; 16-bit mode, PPN_TRAIN_FUSE_STATS=0: off): a forward
+    # convolution that feeds a BatchNorm folds {sum y, sum y^2} per pixel tile, an input-gradient convolution whose result is a
+    # BatchNorm's dy folds {sum g, sum g * xhat}, a BatchNorm whose result is the next BatchNorm's input / dy folds them in its apply
+    # pass -- the BatchNorm call that follows then skips its own pass over the tensor(s).  Every helper returns the ConvStats in a
+    # fixed slot, None where there are none.
     def _bn(self, x, prefix, act, stats=None, emit=False):
-        """emit: the output is the input of the next unit's BatchNorm -> (y, saved, ConvStats) (train.bn_train_forward)"""
-        return T.bn_train_forward(x, self.P[prefix + ".weight"], self.P[prefix + ".bias"],
-                                  self.buffers[prefix + ".running_mean"], self.buffers[prefix + ".running_var"],
-                                  act=act, stats=stats, emit_stats=emit and self._fuse_stats)
+        """-> (y, saved, ConvStats or None); emit: y is the input of the next unit's BatchNorm (train.bn_train_forward)"""
+        emit = emit and self._fuse_stats
+        r = T.bn_train_forward(x, self.P[prefix + ".weight"], self.P[prefix + ".bias"],
+                               self.buffers[prefix + ".running_mean"], self.buffers[prefix + ".running_var"],
+                               act=act, stats=stats, emit_stats=emit)
+        return r[0], r[1], (r[2] if emit else None)
+
+    def _bn_desc(self, bn):
+        """(x, prefix, act, saved) -> the (x, gamma, beta, saved, act) train.py takes"""
+        x, prefix, act, saved = bn
+        return x, self.P[prefix + ".weight"], self.P[prefix + ".bias"], saved, act
 
     def _bn_bwd(self, x, dy, prefix, act, saved, dx_add=None, keep=True, stats=None, next_bn=None):
-        """next_bn = (x2, prefix2, act2, saved2): dx is the dy of that BatchNorm -> (dx, ConvStats) (train.bn_train_backward)"""
+        """-> (dx, ConvStats or None); next_bn = (x2, prefix2, act2, saved2): dx is the dy of that BatchNorm (train.bn_train_backward)"""
         # parameter gradients land directly in the flat gradient buffer (probe passes discard them)
-        if next_bn is not None and self._fuse_stats:
-            x2, p2, act2, saved2 = next_bn
-            nb = (x2, self.P[p2 + ".weight"], self.P[p2 + ".bias"], saved2, act2)
-        else:
-            nb = None
+        nb = self._bn_desc(next_bn) if next_bn is not None and self._fuse_stats else None
         r = T.bn_train_backward(x, dy, self.P[prefix + ".weight"], self.P[prefix + ".bias"], saved, act=act,
                                 dx_add=dx_add, dgamma=self.G[prefix + ".weight"] if keep else None,
                                 dbeta=self.G[prefix + ".bias"] if keep else None, stats=stats, next_bn=nb)
-        if next_bn is not None:
-            return r[0], (r[3] if nb is not None else None)
-        return r[0]
+        return r[0], (r[3] if nb is not None else None)
 
-    # BatchNorm statistics from the neighbouring convolution's epilogue (train.ConvStats; 16-bit mode, PPN_TRAIN_FUSE_STATS=0: off):
-    # a forward convolution that feeds a BatchNorm folds {sum y, sum y^2} per pixel tile, an input-gradient convolution whose result
-    # is a BatchNorm's dy folds {sum g, sum g * xhat} -- the BatchNorm call that follows then skips its own pass over the tensor(s).
     def _conv_bn(self, x, wname, *args, **kw):
         """conv2d_nhwc whose output feeds a BatchNorm: (y, ConvStats or None)"""
         if self._fuse_stats:
             return T.conv2d_nhwc(x, self.P[wname], *args, stats="fwd", **kw)
         return T.conv2d_nhwc(x, self.P[wname], *args, **kw), None
 
-    def _dgrad_bn(self, dy, wname_or_w, in_hw, stride, dil, pad, x, prefix, act, saved, fuse=True):
-        """conv_dgrad whose result is dy of the BatchNorm `prefix` (+ act) over x: (dx, ConvStats or None)"""
+    def _dgrad_bn(self, dy, wname_or_w, in_hw, stride, dil, pad, bn, fuse=True):
+        """conv_dgrad whose result is dy of the BatchNorm bn = (x, prefix, act, saved), or of none: (dx, ConvStats or None)"""
         w = self.P[wname_or_w] if isinstance(wname_or_w, str) else wname_or_w
-        if self._fuse_stats and fuse and T._FUSE_STATS_BWD:
-            return T.conv_dgrad(dy, w, in_hw, stride, dil, pad,
-                                bn=(x, self.P[prefix + ".weight"], self.P[prefix + ".bias"], saved, act))
+        if bn is not None and self._fuse_stats and fuse and T._FUSE_STATS_BWD:
+            return T.conv_dgrad(dy, w, in_hw, stride, dil, pad, bn=self._bn_desc(bn))
         return T.conv_dgrad(dy, w, in_hw, stride, dil, pad), None
 
     def _on_side(self, fn, *tensors):
@@ -304,93 +475,24 @@ class PPNTrainer:
             self._w3_padded(used)
         # ... every weight view the previous passes of THIS trainer met, in one launch
         T.repack_all(self.device, [self._storage_key] + [ent[2] for ent in self._w3p.values()])
-        tape = []
+        tape = [_UNIT_KINDS[u.kind](u) for u in self.units]
         # the 7x7 stem reads NCHW f32; its weight gradient reads an NHWC copy padded with zero channels: 4 channels for
         # the dedicated bf16 kernel (csrc/stem_wgrad.hip: two MFMAs per filter row), 8 for the generic f32 kernel
         xin8 = torch.empty(B, H, W, 4 if self.tdt == torch.bfloat16 else 8, dtype=self.tdt, device=self.device)
         L.check(lib.ppn_image_to_nhwc(self.compute_dtype, x.data_ptr(), B, H, W, xin8.shape[-1], xin8.data_ptr(),
                                       L.current_stream_ptr()), "ppn_image_to_nhwc")
-        cur = None
-        cur_st = None                                  # ConvStats of `cur` where the next unit opens with a BatchNorm over it
-        for ui, u in enumerate(self.units):
-            nxt_kind = self.units[ui + 1].kind if ui + 1 < len(self.units) else None
-            if u.kind == "cbr":
-                wn = f"{u.prefix}.{u.conv_idx}.weight"
-                bnp = f"{u.prefix}.{u.conv_idx + 1}"
-                d = u.dil[0]
-                if u.k == 7:
-                    y = torch.empty(B, H, W, u.cout, dtype=self.tdt, device=self.device)
-                    L.check(lib.ppn_stem7x7(self.compute_dtype, 0, x.data_ptr(), B, H, W, self.P[wn].data_ptr(), None,
-                                            None, None, None, y.data_ptr(), L.current_stream_ptr()), "ppn_stem7x7")
-                    src = xin8
-                    yst = None
-                else:
-                    src = cur
-                    y, yst = self._conv_bn(cur, wn, u.stride, d, d)
-                emit = self._fuse_stats and nxt_kind in ("basic", "head")   # those open with a BatchNorm over this unit's output
-                r = self._bn(y, bnp, "relu", stats=yst, emit=emit)
-                z, saved, cur_st = r[0], r[1], (r[2] if emit else None)
-                tape.append(("cbr", u, dict(x=src, y=y, saved=saved)))
-                cur = z
-            elif u.kind == "basic":
-                p = u.prefix
-                a, s1 = self._bn(cur, p + ".bn1", "relu", stats=cur_st)
-                cur_st = None
-                c1, c1st = self._conv_bn(a, p + ".conv1.weight", u.stride, u.dil[0], u.dil[0])
-                b, s2 = self._bn(c1, p + ".bn2", "relu", stats=c1st)
-                ctx = dict(x=cur, a=a, s1=s1, c1=c1, b=b, s2=s2)
-                if u.downsample:
-                    dsy, dst = self._conv_bn(cur, p + ".downsample.0.weight", u.stride, 1, 0)
-                    r, s3 = self._bn(dsy, p + ".downsample.1", "none", stats=dst)
-                    ctx.update(dsy=dsy, s3=s3)
-                else:
-                    r = cur
-                out = T.conv2d_nhwc(b, self.P[p + ".conv2.weight"], 1, u.dil[1], u.dil[1], add=r)
-                tape.append(("basic", u, ctx))
-                cur = out
-            elif u.kind == "bottleneck":                              # drn.py:77-97 (post-activation)
-                p, pl = u.prefix, u.planes
-                y1, st1 = self._conv_bn(cur, p + ".conv1.weight")
-                h1, s1 = self._bn(y1, p + ".bn1", "relu", stats=st1)
-                y2, st2 = self._conv_bn(h1, p + ".conv2.weight", u.stride, u.dil[1], u.dil[1])
-                h2, s2 = self._bn(y2, p + ".bn2", "relu", stats=st2)
-                y3, st3 = self._conv_bn(h2, p + ".conv3.weight")
-                z3, s3 = self._bn(y3, p + ".bn3", "none", stats=st3)
-                ctx = dict(x=cur, y1=y1, h1=h1, s1=s1, y2=y2, h2=h2, s2=s2, y3=y3, s3=s3)
-                if u.downsample:
-                    yd, std = self._conv_bn(cur, p + ".downsample.0.weight", u.stride, 1, 0)
-                    r, sd = self._bn(yd, p + ".downsample.1", "none", stats=std)
-                    ctx.update(yd=yd, sd=sd)
-                else:
-                    r = cur
-                out = T.add_relu(z3, r)
-                ctx["out"] = out
-                tape.append(("bottleneck", u, ctx))
-                cur = out
-            else:                                                     # PPN head, model.py:113-136
-                R = cur
-                h0, s0 = self._bn(R, "bn0_1", "lrelu", stats=cur_st)
-                cur_st = None
-                a1, a1st = self._conv_bn(h0, "conv1x1_1.weight")
-                h1, s1 = self._bn(a1, "bn1", "lrelu", stats=a1st)
-                a2, a2st = self._conv_bn(h1, "conv1.weight", 1, 1, 1)
-                h2, s2 = self._bn(a2, "bn0_2", "lrelu", stats=a2st)
-                a3 = T.conv2d_nhwc(h2, self.P["conv1x1_2.weight"], add=R)
-                c2, c2st = self._conv_bn(a3, "conv2.weight", 1, 1, 1, bias=self.P["conv2.bias"])
-                h3, s3 = self._bn(c2, "bn2", "lrelu", stats=c2st)
-                head = T.conv2d_nhwc(h3, self.P["conv3.weight"], bias=self.P["conv3.bias"], act=L.PPN_ACT_SIGMOID,
-                                     nchw_f32=True)
-                tape.append(("head", u, dict(R=R, h0=h0, s0=s0, a1=a1, h1=h1, s1=s1, a2=a2, h2=h2, s2=s2, a3=a3,
-                                             c2=c2, h3=h3, s3=s3, head=head)))
-                cur = head
+        tape[0].x = xin8
+        cur, st = x, None                              # st: ConvStats of `cur` where the next unit opens with a BatchNorm over it
+        for unit, above in zip(tape, tape[1:] + [None]):
+            cur, st = unit.forward(self, cur, st, emit=above is not None and above.opens_with_bn)
         self.num_batches_tracked += 1
         self._tape = tape
         # flat-buffer offset of the unit that follows each unit in forward order (for the bucketed exchange)
         self._next_offset = {}
         nxt = self.flat.numel()
-        for kind, u, _ in reversed(tape):
-            self._next_offset[id(u)] = nxt
-            nxt = self._unit_offset(kind, u)
+        for unit in reversed(tape):
+            self._next_offset[id(unit)] = nxt
+            nxt = self.offset[unit.first]
         return cur
 
     # ---- backward ------------------------------------------------------------------------------------------------
@@ -399,7 +501,7 @@ class PPNTrainer:
         channels_used: only the first so many head channels carry a gradient (6K for the unary losses)."""
         lib = L.load()
         keep = not probe_only
-        head = c["head"]
+        head = c.head
         B, Ch, Ho, Wo = head.shape
         used = Ch if channels_used is None else channels_used
         assert not keep or used == Ch
@@ -416,34 +518,29 @@ class PPNTrainer:
         w3p = self._w3_padded(used)
         if keep:
             def wg3():
-                dw3 = T.conv_wgrad(c["h3"], dz, 1)
+                dw3 = T.conv_wgrad(c.h3, dz, 1)
                 self.G["conv3.weight"].copy_(dw3[:Ch])
-            self._on_side(wg3, c["h3"], dz)
+            self._on_side(wg3, c.h3, dz)
         # (the probe passes keep the separate reduction pass: their stacked form -- _stacked_unary_probe_grads, several gradient
         # streams per launch -- has no fused sums, and the two forms stay bit-identical)
-        dh3, st3 = self._dgrad_bn(dz, w3p, (Ho, Wo), 1, 1, 0, c["c2"], "bn2", "lrelu", c["s3"], fuse=keep)
-        dc2 = self._bn_bwd(c["c2"], dh3, "bn2", "lrelu", c["s3"], keep=keep, stats=st3)
+        dh3, st3 = self._dgrad_bn(dz, w3p, (Ho, Wo), 1, 1, 0, (c.c2, "bn2", "lrelu", c.s3), fuse=keep)
+        dc2, _ = self._bn_bwd(c.c2, dh3, "bn2", "lrelu", c.s3, keep=keep, stats=st3)
         if keep:
-            ws = T._workspace(dc2.shape[-1], self.device)
-            L.check(lib.ppn_colsum(self.compute_dtype, dc2.data_ptr(), dc2.numel() // dc2.shape[-1], dc2.shape[-1],
-                                   self.G["conv2.bias"].data_ptr(), ws.data_ptr(), L.current_stream_ptr()),
-                    "ppn_colsum")
-            self._wgrad("conv2.weight", c["a3"], dc2, 3, 1, 1, 1)
+            T.colsum(dc2, self.G["conv2.bias"], self.device)
+            self._wgrad("conv2.weight", c.a3, dc2, 3, 1, 1, 1)
         da3 = T.conv_dgrad(dc2, self.P["conv2.weight"], (Ho, Wo), 1, 1, 1)
         if keep:
-            self._wgrad("conv1x1_2.weight", c["h2"], da3, 1)
-        dh2, st2 = self._dgrad_bn(da3, "conv1x1_2.weight", (Ho, Wo), 1, 1, 0, c["a2"], "bn0_2", "lrelu", c["s2"], fuse=keep)
-        da2 = self._bn_bwd(c["a2"], dh2, "bn0_2", "lrelu", c["s2"], keep=keep, stats=st2)
+            self._wgrad("conv1x1_2.weight", c.h2, da3, 1)
+        dh2, st2 = self._dgrad_bn(da3, "conv1x1_2.weight", (Ho, Wo), 1, 1, 0, (c.a2, "bn0_2", "lrelu", c.s2), fuse=keep)
+        da2, _ = self._bn_bwd(c.a2, dh2, "bn0_2", "lrelu", c.s2, keep=keep, stats=st2)
         if probe_only:
-            return T.conv_wgrad(c["h1"], da2, 3, 1, 1, 1)
-        self._wgrad("conv1.weight", c["h1"], da2, 3, 1, 1, 1)
+            return T.conv_wgrad(c.h1, da2, 3, 1, 1, 1)
+        self._wgrad("conv1.weight", c.h1, da2, 3, 1, 1, 1)
         second = so is not None and "head" in so
-        if second:                                       # the second-order adjoint is added to dh1 below: no sums of the bare dh1
-            dh1, st1 = T.conv_dgrad(da2, self.P["conv1.weight"], (Ho, Wo), 1, 1, 1), None
-        else:
-            dh1, st1 = self._dgrad_bn(da2, "conv1.weight", (Ho, Wo), 1, 1, 1, c["a1"], "bn1", "lrelu", c["s1"])
+        # (second: the second-order adjoint is added to dh1 below -- no sums of the bare dh1)
+        dh1, st1 = self._dgrad_bn(da2, "conv1.weight", (Ho, Wo), 1, 1, 1, None if second else (c.a1, "bn1", "lrelu", c.s1))
         skip = da3
-        if so is not None and "head" in so:
+        if second:
             # GradNorm's Lgrad.backward(): the second-order adjoints at h1 and at the skip tensor join the first-order
             # ones here, so everything upstream is back-propagated once
             if so.get("launch_probes") is not None:
@@ -452,11 +549,11 @@ class PPNTrainer:
             if h1_sum is not None:
                 dh1 = h1_sum                             # first-order seed + second-order adjoint (added in a conv epilogue)
                 skip = da3 + r_bar
-        da1 = self._bn_bwd(c["a1"], dh1, "bn1", "lrelu", c["s1"], stats=st1)
-        self._wgrad("conv1x1_1.weight", c["h0"], da1, 1)
-        dh0, st0 = self._dgrad_bn(da1, "conv1x1_1.weight", (Ho, Wo), 1, 1, 0, c["R"], "bn0_1", "lrelu", c["s0"])
-        # next_bn: the BatchNorm of the unit below that takes this gradient as its dy -> (dR, ConvStats)
-        return self._bn_bwd(c["R"], dh0, "bn0_1", "lrelu", c["s0"], dx_add=skip, stats=st0, next_bn=next_bn)
+        da1, _ = self._bn_bwd(c.a1, dh1, "bn1", "lrelu", c.s1, stats=st1)
+        self._wgrad("conv1x1_1.weight", c.h0, da1, 1)
+        dh0, st0 = self._dgrad_bn(da1, "conv1x1_1.weight", (Ho, Wo), 1, 1, 0, (c.R, "bn0_1", "lrelu", c.s0))
+        # next_bn: the BatchNorm of the unit below that takes this gradient as its dy -> (dR, ConvStats or None)
+        return self._bn_bwd(c.R, dh0, "bn0_1", "lrelu", c.s0, dx_add=skip, stats=st0, next_bn=next_bn)
 
     # ---- second order ------------------------------------------------------------------------------------------------
     def _second_order_tail(self, c, so, dh1=None):
@@ -486,7 +583,7 @@ class PPNTrainer:
         # the tangents are rebuilt for the streams that are active -- bitwise the results of the non-speculative order (both multiply by
         # the SAME device-computed reciprocal, see inv_dev).
         total = self.G["conv1.weight"]
-        trusted = coeff[4] > 1e-3 * max(coeff)
+        trusted = T.limb_remainder_trusted(coeff, self.compute_dtype)
         spec = None
         if trusted:
             gw4, st = T.probe_stats(gw, total.contiguous(), coeff)
@@ -504,10 +601,7 @@ class PPNTrainer:
                 spec = self._tail_tangents(c, [(g * inv_dev[i]) for i, g in enumerate(gw + [gw4])], list(range(5)))
             ev.synchronize()
             host = self._so_pin.tolist()
-            if self.compute_dtype != L.PPN_F32:
-                # bf16: `total` and the unary probes come from differently rounded passes (relative noise ~2^-8 each);
-                # a remainder that is not clearly above that noise cannot be trusted (see _limb_probe)
-                trusted = host[5] > (16.0 * 2.0 ** -8) ** 2 * host[6]
+            trusted = T.limb_remainder_trusted(coeff, self.compute_dtype, host[5], host[6])
         inv_h = None
         if trusted:
             ss = host[:5]
@@ -521,17 +615,16 @@ class PPNTrainer:
                               self.base.reshape(5)]).tolist()
             ss = host[:5]
             host = ss + [0.0, 0.0] + host[5:]
-        import numpy as _np
-        f32 = _np.float32
-        gn_np = _np.sqrt(_np.asarray(ss, dtype=f32))
+        f32 = np.float32
+        gn_np = np.sqrt(np.asarray(ss, dtype=f32))
         gn = torch.from_numpy(gn_np).to(self.device, non_blocking=True)
         so["gnorm"] = gn
-        w_np = _np.asarray(self.task.host_weights(), dtype=f32)
-        loss_np, base_np = _np.asarray(host[7:12], dtype=f32), _np.asarray(host[12:17], dtype=f32)
-        G = _np.abs(w_np) * gn_np                                                 # main.py:717-721
+        w_np = np.asarray(self.task.host_weights(), dtype=f32)
+        loss_np, base_np = np.asarray(host[7:12], dtype=f32), np.asarray(host[12:17], dtype=f32)
+        G = np.abs(w_np) * gn_np                                                 # main.py:717-721
         lhat = w_np * loss_np / base_np
         Cc = G.mean(dtype=f32) * (lhat / lhat.mean(dtype=f32)) ** f32(self.task.alpha)   # main.py:726-753 (constant)
-        kappa = (_np.sign(G - Cc) * _np.sign(w_np) * _np.abs(w_np)).tolist()      # d Lgrad / d||g_i||, times w_i
+        kappa = (np.sign(G - Cc) * np.sign(w_np) * np.abs(w_np)).tolist()      # d Lgrad / d||g_i||, times w_i
         gn_h = gn_np.tolist()
         k6 = 6 * cfg.K
         P, Gd = self.P, self.G
@@ -576,10 +669,10 @@ class PPNTrainer:
             # Weight gradients are leaves here too: on the side stream (idle during the tail) instead of ~0.9 ms of the
             # main stream; they accumulate into gradients the side stream wrote, so the order is the stream's own.
             def wg3(zsum=zsum, th3=th3, tzb=tzb, used=used):
-                dw3 = T.conv_wgrad(c["h3"], zsum, 1)                              # primal stream: same h3 for all
+                dw3 = T.conv_wgrad(c.h3, zsum, 1)                              # primal stream: same h3 for all
                 T.conv_wgrad(th3, tzb, 1, out=dw3, accumulate=True)              # tangent stream: stacked batch
                 Gd["conv3.weight"][:used] += dw3[:used]
-            self._tail_side(wg3, c["h3"], zsum, th3, tzb)
+            self._tail_side(wg3, c.h3, zsum, th3, tzb)
             Gd["conv3.bias"][:used] += zbias
             T.conv_dgrad(zsum, w3p, (Ho, Wo), add=None if first_group else H3sum, out=H3sum)
             first_group = False
@@ -589,28 +682,28 @@ class PPNTrainer:
         # of the summed primal adjoint and of the n tangent adjoints are 1 + n streams of one call; the n dual terms
         # accumulate into the one primal result): 8 + n launches per BN layer where the stream-by-stream form took 12 n.
         both = torch.empty((1 + n) * B, *TC2.shape[1:], dtype=self.tdt, device=self.device)   # [sum of primal adj | tangent adj]
-        c2sum, TC2bar, dg, db = T.bn_dual_backward_summed(c["c2"], TC2, HB, P["bn2.weight"], P["bn2.bias"], c["s3"], "lrelu",
+        c2sum, TC2bar, dg, db = T.bn_dual_backward_summed(c.c2, TC2, HB, P["bn2.weight"], P["bn2.bias"], c.s3, "lrelu",
                                                           n, out_both=both)
         Gd["bn2.weight"] += dg
         Gd["bn2.bias"] += db
         Gd["conv2.bias"] += c2sum.float().sum((0, 1, 2))
         def wg2(c2sum=c2sum, TC2bar=TC2bar):
-            T.conv_wgrad(c["a3"], c2sum, 3, 1, 1, 1, out=Gd["conv2.weight"], accumulate=True)
+            T.conv_wgrad(c.a3, c2sum, 3, 1, 1, 1, out=Gd["conv2.weight"], accumulate=True)
             T.conv_wgrad(TA3, TC2bar, 3, 1, 1, 1, out=Gd["conv2.weight"], accumulate=True)
-        self._tail_side(wg2, c["a3"], c2sum, TA3, TC2bar)
+        self._tail_side(wg2, c.a3, c2sum, TA3, TC2bar)
         both = T.conv_dgrad(both, P["conv2.weight"], (Ho, Wo), 1, 1, 1)
         a3sum, TA3bar = both[:B], both[B:]
         def wg12(a3sum=a3sum, TA3bar=TA3bar):
-            T.conv_wgrad(c["h2"], a3sum, 1, out=Gd["conv1x1_2.weight"], accumulate=True)
+            T.conv_wgrad(c.h2, a3sum, 1, out=Gd["conv1x1_2.weight"], accumulate=True)
             T.conv_wgrad(TH2, TA3bar, 1, out=Gd["conv1x1_2.weight"], accumulate=True)
-        self._tail_side(wg12, c["h2"], a3sum, TH2, TA3bar)
+        self._tail_side(wg12, c.h2, a3sum, TH2, TA3bar)
         both = T.conv_dgrad(both, P["conv1x1_2.weight"], (Ho, Wo))                # [sum of H2bar | TH2bar]
-        a2sum, U_bar, dg, db = T.bn_dual_backward_summed(c["a2"], u2, both, P["bn0_2.weight"], P["bn0_2.bias"], c["s2"],
+        a2sum, U_bar, dg, db = T.bn_dual_backward_summed(c.a2, u2, both, P["bn0_2.weight"], P["bn0_2.bias"], c.s2,
                                                          "lrelu", n)
         Gd["bn0_2.weight"] += dg
         Gd["bn0_2.bias"] += db
-        self._tail_side(lambda: T.conv_wgrad(c["h1"], a2sum, 3, 1, 1, 1, out=Gd["conv1.weight"], accumulate=True),
-                        c["h1"], a2sum)
+        self._tail_side(lambda: T.conv_wgrad(c.h1, a2sum, 3, 1, 1, 1, out=Gd["conv1.weight"], accumulate=True),
+                        c.h1, a2sum)
         # adjoint at h1: through W (primal) and through u_i = conv(h1, v_i) per stream; every convolution adds the sum so
         # far in its epilogue (f32, one rounding) instead of a separate elementwise pass
         # (dh1: the first-order gradient at h1 joins here, in the first epilogue of the chain, instead of a pass of its own)
@@ -628,18 +721,18 @@ class PPNTrainer:
         channels: their streams share 128-channel conv3 launches.  Needs no host value (see _second_order_tail)."""
         P = self.P
         n = len(act)
-        B = c["h1"].shape[0]
-        Ch = c["head"].shape[1]
+        B = c.h1.shape[0]
+        Ch = c.head.shape[1]
         k6 = 6 * cfg.K
         vs = [v.contiguous() for v in vs]
-        u2 = torch.empty(n * B, *c["a2"].shape[1:], dtype=self.tdt, device=self.device)   # the streams back to back
+        u2 = torch.empty(n * B, *c.a2.shape[1:], dtype=self.tdt, device=self.device)   # the streams back to back
         for j, v in enumerate(vs):
-            T.conv2d_nhwc(c["h1"], v, 1, 1, 1, out=u2[j * B:(j + 1) * B])
+            T.conv2d_nhwc(c.h1, v, 1, 1, 1, out=u2[j * B:(j + 1) * B])
         # the BN tangents of all streams in one set of launches (ppn_bn_*_streams: per-stream batch statistics, shared x)
-        TH2 = T.bn_tangent(c["a2"], u2, P["bn0_2.weight"], P["bn0_2.bias"], c["s2"], "lrelu", nstreams=n)
+        TH2 = T.bn_tangent(c.a2, u2, P["bn0_2.weight"], P["bn0_2.bias"], c.s2, "lrelu", nstreams=n)
         TA3 = T.conv2d_nhwc(TH2, P["conv1x1_2.weight"])
         TC2 = T.conv2d_nhwc(TA3, P["conv2.weight"], 1, 1, 1)
-        TH3 = T.bn_tangent(c["c2"], TC2, P["bn2.weight"], P["bn2.bias"], c["s3"], "lrelu", nstreams=n)
+        TH3 = T.bn_tangent(c.c2, TC2, P["bn2.weight"], P["bn2.bias"], c.s3, "lrelu", nstreams=n)
         tz_groups = []
         for js, used in (([j for j, i in enumerate(act) if i < 4], k6), ([j for j, i in enumerate(act) if i == 4], Ch)):
             if not js:
@@ -665,14 +758,6 @@ class PPNTrainer:
             ent[0] = T._param_version[0]
         return ent[1]
 
-    def _unit_offset(self, kind, u) -> int:
-        """First element of the flat buffer that belongs to this unit (its parameters are contiguous)."""
-        if kind == "head":
-            return self.offset["conv1x1_1.weight"]
-        if kind in ("basic", "bottleneck"):
-            return self.offset[u.prefix + ".conv1.weight"]
-        return self.offset[f"{u.prefix}.{u.conv_idx}.weight"]
-
     def backward(self, grad_head: torch.Tensor, exchange: Optional["T.BucketedAllReduce"] = None, so=None):
         """d(sum_i coeff_i L_i)/d(theta) into self.grad, given d/d(head) from the loss kernel.  `exchange`: buckets
         of the flat buffer are all-reduced as soon as the units that own them are done (the buffer is in forward
@@ -684,110 +769,24 @@ class PPNTrainer:
             if self._side is not None:
                 torch.cuda.current_stream(self.device).wait_stream(self._side)
 
-        g = grad_head
-        gst = None                                       # ConvStats of g where g is the dy of the NEXT unit's leading BatchNorm
-        order = list(reversed(self._tape))
-        for ui, (kind, u, c) in enumerate(order):
-            # the unit BEFORE this one in forward order: a conv-BN-ReLU unit's BatchNorm takes this unit's input gradient as its dy
-            below = order[ui + 1] if ui + 1 < len(order) else None
-            below_cbr = below is not None and below[0] == "cbr"
-            # ... and a block with a projection shortcut takes it as the dy of the shortcut's BatchNorm: (x2, prefix2, act2, saved2)
-            if below_cbr:
-                below_bn = (below[2]["y"], f"{below[1].prefix}.{below[1].conv_idx + 1}", "relu", below[2]["saved"])
-            elif below is not None and below[0] == "basic" and below[1].downsample:
-                below_bn = (below[2]["dsy"], below[1].prefix + ".downsample.1", "none", below[2]["s3"])
-            else:
-                below_bn = None
-            if exchange is not None and kind != "head":
+        order = self._tape[::-1]
+        g, gst = grad_head, None                         # gst: ConvStats of g where g is the dy of the unit's entry_bn()
+        for unit, below in zip(order, order[1:] + [None]):
+            is_head = isinstance(unit, _Head)
+            if exchange is not None and not is_head:
                 # every unit AFTER this one in forward order has been processed: its slice of the buffer is final
-                nxt = self._next_offset[id(u)]
-                exchange.ready(nxt, before_issue=join_side)
-            if kind == "head":
-                if below_bn is not None:
-                    g, gst = self._head_backward(c, g, probe_only=False, so=so, next_bn=below_bn)
-                else:
-                    g = self._head_backward(c, g, probe_only=False, so=so)
-                if exchange is not None and exchange.enabled:
-                    # the GradNorm probes need THIS rank's d loss/d conv1.weight; keep it before its bucket is summed
-                    join_side()
-                    self._conv1_local = self.G["conv1.weight"].clone()
-            elif kind == "basic":
-                p = u.prefix
-                hw = c["x"].shape[1:3]
-                if u.downsample:
-                    # first: its BatchNorm may take the sums the unit above folded while it wrote g (gst), and they sit in the
-                    # workspace every BatchNorm / statistics epilogue of this channel count uses
-                    dds = self._bn_bwd(c["dsy"], g, p + ".downsample.1", "none", c["s3"], stats=gst)
-                    self._wgrad(p + ".downsample.0.weight", c["x"], dds, 1, u.stride, 1, 0)
-                    dxr = T.conv_dgrad(dds, self.P[p + ".downsample.0.weight"], hw, u.stride, 1, 0)
-                else:
-                    dxr = g
-                gst = None
-                self._wgrad(p + ".conv2.weight", c["b"], g, 3, 1, u.dil[1], u.dil[1])
-                db, dbst = self._dgrad_bn(g, p + ".conv2.weight", c["b"].shape[1:3], 1, u.dil[1], u.dil[1],
-                                          c["c1"], p + ".bn2", "relu", c["s2"])
-                dc1 = self._bn_bwd(c["c1"], db, p + ".bn2", "relu", c["s2"], stats=dbst)
-                self._wgrad(p + ".conv1.weight", c["a"], dc1, 3, u.stride, u.dil[0], u.dil[0])
-                da, dast = self._dgrad_bn(dc1, p + ".conv1.weight", hw, u.stride, u.dil[0], u.dil[0],
-                                          c["x"], p + ".bn1", "relu", c["s1"])
-                if below_bn is not None:
-                    g, gst = self._bn_bwd(c["x"], da, p + ".bn1", "relu", c["s1"], dx_add=dxr, stats=dast, next_bn=below_bn)
-                else:
-                    g = self._bn_bwd(c["x"], da, p + ".bn1", "relu", c["s1"], dx_add=dxr, stats=dast)
-            elif kind == "bottleneck":
-                p = u.prefix
-                hw = c["x"].shape[1:3]
-                dsum = T.relu_mask(c["out"], g)                              # through relu(z3 + r)
-                dy3 = self._bn_bwd(c["y3"], dsum, p + ".bn3", "none", c["s3"])
-                self._wgrad(p + ".conv3.weight", c["h2"], dy3, 1)
-                dh2, dh2st = self._dgrad_bn(dy3, p + ".conv3.weight", c["h2"].shape[1:3], 1, 1, 0, c["y2"], p + ".bn2", "relu", c["s2"])
-                dy2 = self._bn_bwd(c["y2"], dh2, p + ".bn2", "relu", c["s2"], stats=dh2st)
-                self._wgrad(p + ".conv2.weight", c["h1"], dy2, 3, u.stride, u.dil[1], u.dil[1])
-                dh1, dh1st = self._dgrad_bn(dy2, p + ".conv2.weight", c["h1"].shape[1:3], u.stride, u.dil[1], u.dil[1],
-                                            c["y1"], p + ".bn1", "relu", c["s1"])
-                dy1 = self._bn_bwd(c["y1"], dh1, p + ".bn1", "relu", c["s1"], stats=dh1st)
-                self._wgrad(p + ".conv1.weight", c["x"], dy1, 1)
-                if u.downsample:
-                    dyd = self._bn_bwd(c["yd"], dsum, p + ".downsample.1", "none", c["sd"])
-                    self._wgrad(p + ".downsample.0.weight", c["x"], dyd, 1, u.stride, 1, 0)
-                    dxr = T.conv_dgrad(dyd, self.P[p + ".downsample.0.weight"], hw, u.stride, 1, 0)
-                else:
-                    dxr = dsum
-                g = T.conv_dgrad(dy1, self.P[p + ".conv1.weight"], hw, add=dxr)
-                gst = None
-            else:  # cbr
-                wn = f"{u.prefix}.{u.conv_idx}.weight"
-                bnp = f"{u.prefix}.{u.conv_idx + 1}"
-                d = u.dil[0]
-                dy = self._bn_bwd(c["y"], g, bnp, "relu", c["saved"], stats=gst)
-                gst = None
-                if u.k == 7:
-                    def wg0(x8=c["x"], dy=dy, wn=wn):
-                        dw8 = T.conv_wgrad(x8, dy, 7, 1, 1, 3)            # [16, 4 | 8, 7, 7]; input channels 3.. are zero
-                        self.G[wn].copy_(dw8[:, :3])
-                    # the LAST weight gradient of the pass: on the main stream (idle from here on) beside the side stream's
-                    # layer1 / layer2 weight gradients instead of behind them (PPN_TRAIN_WG0_MAIN=0: on the side stream)
-                    if self._wg0_main:
-                        wg0()
-                    else:
-                        self._on_side(wg0, c["x"], dy)
-                    g = None                                               # the input needs no gradient
-                else:
-                    self._wgrad(wn, c["x"], dy, 3, u.stride, d, d)
-                    if below_bn is not None:                               # g is the dy of a BatchNorm of the unit below
-                        g, gst = self._dgrad_bn(dy, wn, c["x"].shape[1:3], u.stride, d, d, below_bn[0], below_bn[1],
-                                                below_bn[2], below_bn[3])
-                    else:
-                        g = T.conv_dgrad(dy, self.P[wn], c["x"].shape[1:3], u.stride, d, d)
-        if self._side is not None:
-            torch.cuda.current_stream(self.device).wait_stream(self._side)   # every weight gradient has landed
+                exchange.ready(self._next_offset[id(unit)], before_issue=join_side)
+            g, gst = unit.backward(self, g, gst, below.entry_bn() if below is not None else None, so)
+            if is_head and exchange is not None and exchange.enabled:
+                # the GradNorm probes need THIS rank's d loss/d conv1.weight; keep it before its bucket is summed
+                join_side()
+                self._conv1_local = self.G["conv1.weight"].clone()
+        join_side()                                      # every weight gradient has landed
         return self.grad
 
     def probe_grad(self, grad_head: torch.Tensor, channels_used: Optional[int] = None) -> torch.Tensor:
         """dL/dW for W = head conv1.weight (params[-13]) from d L/d(head): the partial backward of main.py:704-708."""
-        kind, _, c = self._tape[-1]
-        assert kind == "head"
-        return self._head_backward(c, grad_head, probe_only=True, channels_used=channels_used)
+        return self._head_backward(self._tape[-1], grad_head, probe_only=True, channels_used=channels_used)
 
     def _stacked_unary_probe_grads(self, head, targets, scratch):
         """[dL_i/dW for i < 4] (W = conv1.weight, the four unary losses): the four probe passes of probe_grad() with their
@@ -795,8 +794,7 @@ class PPNTrainer:
         (they are per-image operations) -- the BN backward passes (per-pass batch statistics) take the pass as a grid dimension
         and only the four weight gradients run pass by pass: 25 launches instead of 68, and three well-filled convolution launches instead of twelve
         at a quarter of the GPU.  Same arithmetic per element as probe_grad(): the results are bit-identical."""
-        kind, _, c = self._tape[-1]
-        assert kind == "head"
+        c = self._tape[-1]
         lib = L.load()
         B, Ch, Ho, Wo = head.shape
         k6 = 6 * cfg.K
@@ -808,12 +806,12 @@ class PPNTrainer:
                                       dz4[i * B:(i + 1) * B].data_ptr(), None, L.current_stream_ptr()), "ppn_head_grad")
         dh3 = T.conv_dgrad(dz4, self._w3_padded(k6), (Ho, Wo))
         # the BN backward of the four passes in one set of launches (per-pass batch statistics: the pass is a grid dimension)
-        dc2, _, _ = T.bn_train_backward(c["c2"], dh3, self.P["bn2.weight"], self.P["bn2.bias"], c["s3"], act="lrelu", nstreams=4)
+        dc2, _, _ = T.bn_train_backward(c.c2, dh3, self.P["bn2.weight"], self.P["bn2.bias"], c.s3, act="lrelu", nstreams=4)
         da3 = T.conv_dgrad(dc2, self.P["conv2.weight"], (Ho, Wo), 1, 1, 1)
         dh2 = T.conv_dgrad(da3, self.P["conv1x1_2.weight"], (Ho, Wo))
-        da2, _, _ = T.bn_train_backward(c["a2"], dh2, self.P["bn0_2.weight"], self.P["bn0_2.bias"], c["s2"], act="lrelu",
+        da2, _, _ = T.bn_train_backward(c.a2, dh2, self.P["bn0_2.weight"], self.P["bn0_2.bias"], c.s2, act="lrelu",
                                         nstreams=4)
-        return [T.conv_wgrad(c["h1"], da2[i * B:(i + 1) * B], 3, 1, 1, 1) for i in range(4)]
+        return [T.conv_wgrad(c.h1, da2[i * B:(i + 1) * B], 3, 1, 1, 1) for i in range(4)]
 
     def _unary_probes(self, head, targets, coeff, scratch):
         """The four cheap probe passes: (gnorm[0:4] f32[4], sum_{i<4} coeff_i dL_i/dW).  Independent of backward()."""
@@ -829,18 +827,15 @@ class PPNTrainer:
 
     def _limb_probe(self, total, acc, coeff, head, targets) -> torch.Tensor:
         """dL_4/dW (limb loss) = (sum_i coeff_i dL_i/dW - sum_{i<4} coeff_i dL_i/dW) / coeff_4 by linearity of the
-        backward pass, or the direct fifth pass when that remainder cannot be trusted: coeff_4 too small to divide by,
-        or -- bf16 mode, where `total` and `acc` come from differently rounded passes (relative noise ~2^-8 each) -- a
-        remainder that is not clearly above the rounding noise of the total."""
-        if coeff[4] > 1e-3 * max(coeff):
+        backward pass, or the direct fifth pass when that remainder cannot be trusted (train.limb_remainder_trusted)."""
+        if T.limb_remainder_trusted(coeff, self.compute_dtype):
             rest = total - acc
-            trusted = True
+            n_rest = n_tot = None
             if self.compute_dtype != L.PPN_F32:
                 # both norms in one device tensor: ONE read-back (a host sync on the main stream) instead of two
                 n_rest, n_tot = torch.stack([T.sumsq(rest.contiguous().view(-1)).reshape(()),
                                              T.sumsq(total.contiguous().view(-1)).reshape(())]).tolist()
-                trusted = n_rest > (16.0 * 2.0 ** -8) ** 2 * n_tot
-            if trusted:
+            if T.limb_remainder_trusted(coeff, self.compute_dtype, n_rest, n_tot):
                 return rest / float(coeff[4])
         _, g4 = self.criterion.forward_backward(head, targets, coeff=[0.0, 0.0, 0.0, 0.0, 1.0])
         return self.probe_grad(g4)
@@ -969,12 +964,11 @@ class PPNTrainer:
                 t.record_stream(main)
             coeff = [v / 5.0 for v in self.task.host_weights()]
             local = self._conv1_local if self._conv1_local is not None else self.G["conv1.weight"]
-            trusted = coeff[4] > 1e-3 * max(coeff)
+            trusted = T.limb_remainder_trusted(coeff, self.compute_dtype)
             if trusted:
                 gw4, st = T.probe_stats([g.contiguous() for g in gs], local.contiguous(), coeff)
-                if self.compute_dtype != L.PPN_F32:
-                    n_rest, n_tot = st[5:7].tolist()                    # the trust test of _limb_probe
-                    trusted = n_rest > (16.0 * 2.0 ** -8) ** 2 * n_tot
+                if self.compute_dtype != L.PPN_F32:                     # (f32: no read-back)
+                    trusted = T.limb_remainder_trusted(coeff, self.compute_dtype, *st[5:7].tolist())
             if trusted:
                 gn = torch.sqrt(st[:5])
             else:
