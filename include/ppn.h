@@ -75,6 +75,9 @@ size_t ppn_decode_workspace_bytes(const ppn_decode_cfg* cfg, int32_t batch);
  * out_bbox   f32 [batch, max_humans, K, 4]        (ymin,xmin,ymax,xmax)  datatest.py:80-86
  * out_score  f32 [batch, max_humans, K]           delta = resp*conf of accepted keypoints
  * Humans are ordered by descending root score (datatest.py:103,139); equal scores by ascending cell.
+ * Grids of up to H*W <= 704 cells (for K = 18, E = 17; 22 x 32 is one of the largest): the parse workgroup keeps its
+ * tables in 160 KB of LDS.  A larger grid returns PPN_E_UNSUPPORTED before anything is launched, here and in
+ * ppn_decode_fused / ppn_decode_fused_ws; ppn_limb_argmax alone has no such limit.
  */
 int ppn_decode(const ppn_decode_cfg* cfg, const float* head, int32_t batch, void* workspace,
                int32_t* out_count, int32_t* out_kp_cell, int32_t* out_limb_arg, float* out_bbox,
@@ -104,7 +107,9 @@ int ppn_limb_argmax(const ppn_decode_cfg* cfg, const float* head, int32_t batch,
 /*
  * datatest.py:134-160 non_maximum_suppression.  bbox f32 [n,4] (ymin,xmin,ymax,xmax) on device,
  * score f32 [n] or NULL, limit <= 0 means None.  out_sel i32 [n] receives the selected indices in the
- * reference's order (descending score when score is given), out_count i32 [1].  n <= 1024.
+ * reference's order (descending score when score is given; equal scores, -0.0 and +0.0 included, by ascending
+ * index), out_count i32 [1].  n <= 998: the pairwise bit matrix and the sort live in 160 KB of LDS, and a larger n
+ * returns PPN_E_UNSUPPORTED before anything is launched.
  */
 int ppn_nms(const float* bbox, const float* score, int32_t n, float thresh, int32_t limit, int32_t* out_sel,
             int32_t* out_count, void* stream);

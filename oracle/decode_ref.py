@@ -16,7 +16,8 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import 
 
 Documented tie rule (the reference's `score.argsort()[::-1]` order is implementation
 defined for equal scores): candidates are ordered by descending
-score, equal scores by ascending row-major cell index.  Fixtures have distinct scores.
+score, equal scores by ascending row-major cell index.  -0.0 and +0.0 are equal scores.  The golden fixtures have
+distinct scores; tests/decode_cases.py builds the tied ones.
 """
 from __future__ import annotations
 

@@ -724,11 +724,13 @@ nms_kernel(const float* __restrict__ bbox, const float* __restrict__ score, int 
     int* s_misc = reinterpret_cast<int*>(carve(16));
     const int t = threadIdx.x;
     if (t < n) {
-        // order = score.argsort()[::-1] (descending; ties by ascending index); input order without score
+        // order = score.argsort()[::-1] (descending; equal values -- +-0 included -- by ascending index); input order
+        // without score
         // monotonic float->uint map so that an ascending key means a descending float value
         unsigned k = 0u;
         if (score) {
-            const unsigned u = __float_as_uint(score[t]);
+            unsigned u = __float_as_uint(score[t]);
+            if (u == 0x80000000u) u = 0u;                            // -0.0 == +0.0 by value: index order decides
             const unsigned mono = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // monotonic float->uint
             k = ~mono;
         }

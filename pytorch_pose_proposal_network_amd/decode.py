@@ -158,7 +158,8 @@ def people_agreement(expected: dict, got: dict):
 
 
 class Decoder:
-    """Owns the scratch/output buffers for a fixed (batch, grid) so repeated calls allocate nothing."""
+    """Owns the scratch/output buffers for a fixed (batch, grid) so repeated calls allocate nothing.  Grids of up to
+    704 cells (22 x 32) decode; a larger one raises PPNError (PPN_E_UNSUPPORTED) at the first decode call."""
 
     def __init__(self, batch: int, out_hw=(24, 24), insize_hw=(384, 384), local_grid=(21, 21), det_thr=0.15,
                  nms_thr=0.3, min_kp=1, max_humans: Optional[int] = None, device="cuda"):
@@ -268,7 +269,8 @@ def get_humans_by_feature(delta, x, y, w, h, e, detection_thresh=0.15, min_num_k
 
 
 def non_maximum_suppression(bbox, thresh, score=None, limit=None):
-    """Drop-in for datatest.py:134-160; returns int32 indices (NumPy), computed by ppn_nms on the GPU."""
+    """Drop-in for datatest.py:134-160; returns int32 indices (NumPy), computed by ppn_nms on the GPU.  Equal scores
+    (-0.0 and +0.0 included) keep their index order.  At most 998 boxes: more raises PPNError (PPN_E_UNSUPPORTED)."""
     lib = L.load()
     bb = _dev(bbox).contiguous()
     n = bb.shape[0]

@@ -11,6 +11,7 @@ from pytorch_pose_proposal_network_amd import config as cfg, prng, synth
 
 pytestmark = pytest.mark.gpu
 
+from decode_cases import unary_and_keys as _unary_and_keys  # noqa: E402  (shared with test_decode_edges_gpu.py)
 from test_oracle import make_head  # noqa: E402  (same seeded head generators as the CPU tests)
 
 
@@ -209,18 +210,6 @@ def test_early_root_nms_candidate_cap_boundary():
         exp = D.decode_ref(heads[i])
         assert len(exp["cand"]) == n, (i, len(exp["cand"]), n)
         _assert_same(out[i], exp, f"{n} candidates")
-
-
-def _unary_and_keys(heads):
-    """What the fused head conv leaves for Decoder.decode_fused: the 6K unary channels and one u64 key per (image, edge,
-    cell) = sigmoid value bits << 32 | ~(first arg-max index of the 21x21 window)."""
-    h = torch.from_numpy(heads).cuda()
-    B = h.shape[0]
-    e = h[:, 6 * cfg.K:].reshape(B, len(cfg.EDGES), -1, h.shape[2], h.shape[3])
-    val, _ = e.max(dim=2)
-    first = (e == val.unsqueeze(2)).float().argmax(dim=2)                              # lowest index among ties
-    keys = (val.contiguous().view(torch.int32).to(torch.int64) << 32) | (0xFFFFFFFF - first)
-    return h[:, :6 * cfg.K].contiguous(), keys.contiguous()
 
 
 def test_fused_decode_spread_root_nms_candidate_counts():
