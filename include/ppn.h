@@ -402,6 +402,44 @@ int ppn_conv_split(int32_t dtype, int32_t cin, int32_t cout, int64_t m, int64_t*
 int ppn_ingest_frames(const void* src_bgr, int32_t batch, int32_t src_h, int32_t src_w, void* dst_rgb, int32_t dst_h,
                       int32_t dst_w, int32_t flip, int32_t swap_rb, void* stream);
 
+/*
+ * Train-time augmentation on the device (aug.py:13-160: IAA + ToNormalizedTensor), csrc/augment.hip.  Coordinates are pixel
+ * indices with pixel centres at integers.  Per image the HOST builds the forward map F (source point -> output point:
+ * rotation + isotropic scale about ((w-1)/2, (h-1)/2), minus the crop's (left, top), centre-aligned resize
+ * x' = (x + 0.5) * out_w / w' - 0.5) and F^-1 in float64 and rounds both to f32 [2][3] (row-major: x row, y row); the
+ * kernels use nothing else (augment.sample_params / affine_matrices).  All arithmetic below is f32 / i32 in exactly the
+ * written order (no contraction), so the outputs are bit-exact with tests/augment_ref.py.  Both run on `stream` and
+ * allocate nothing.
+ *
+ * ppn_augment_images: ONE bilinear resampling pass through F^-1.
+ *   src      u8 [batch][src_h][src_w][3] RGB device, pictures padded to a common size (top-left aligned)
+ *   src_hw   i32 [batch][2] device: valid (h, w) of each picture, <= (src_h, src_w)
+ *   inv      f32 [batch][2][3] device
+ *   dst_u8   u8 [batch][out_h][out_w][3] or NULL;  dst_f32  f32 [batch][3][out_h][out_w] or NULL (at least one):
+ *            (float(v) - mean_c) / std_c, mean (0.485, 0.456, 0.406), std (0.229, 0.224, 0.225), no /255 (aug.py:149-153)
+ * Per output pixel (ox, oy): sx = (inv00 * ox + inv01 * oy) + inv02, sy likewise; ix = floorf(sx), fx = sx - ix,
+ * a1 = (int)rintf(fx * 2048), a0 = 2048 - a1 (b0, b1 for y); the taps (ix, iy) .. (ix + 1, iy + 1), a tap outside
+ * [0, w) x [0, h) of THAT picture's valid size contributing 0 (constant border; padding and neighbours are never read);
+ * per channel t0 = p00 * a0 + p01 * a1, t1 = p10 * a0 + p11 * a1, v = (b0 * t0 + b1 * t1 + (1 << 21)) >> 22.
+ * 16-byte plane stores when out_w % 4 == 0 and the outputs are 16 / 4-byte aligned, scalar stores otherwise (same bits).
+ *
+ * ppn_augment_people: the label rules of aug.py:26-133 on the packed arrays of ppn_encode_targets (same layouts; K = the
+ * keypoint count of that layout, people rows of 5 + 2 * (K - 1) floats), one workgroup per image.
+ *   keypoint (0, 0): absent, stays (0, 0).  Otherwise x' = (f00 * x + f01 * y) + f02, y' likewise; kept iff
+ *   0 <= x' < out_w and 0 <= y' < out_h, else (0, 0).  A keypoint that is (0, 0) afterwards loses its visible bit; no bit is
+ *   ever set; hidden keypoints that stay in frame keep their coordinates.
+ *   head box (cx, cy, w, h): corners cx -+ floorf(w / 2), cy -+ floorf(h / 2), all four through F, min / max per axis,
+ *   clipped to [0, out_w] x [0, out_h], stored as ((x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1).  `size` is copied.
+ *   A person whose 2 * (K - 1) keypoint values are all 0 is removed; the survivors keep their order (any pmax);
+ *   count_out[b] = survivors (0 when nobody is left), rows beyond it are zeroed in people_out and visible_out.
+ * The outputs must not alias the inputs.
+ */
+int ppn_augment_images(const uint8_t* src, const int32_t* src_hw, const float* inv, int32_t batch, int32_t src_h,
+                       int32_t src_w, int32_t out_h, int32_t out_w, uint8_t* dst_u8, float* dst_f32, void* stream);
+int ppn_augment_people(const float* people, const int32_t* visible, const int32_t* count, const float* fwd, int32_t batch,
+                       int32_t pmax, int32_t K, int32_t out_h, int32_t out_w, float* people_out, int32_t* visible_out,
+                       int32_t* count_out, void* stream);
+
 /* Process-wide tile choice of the large-tile convolution kernel.  0 (default): one launch at a time -- tiles are
  * sized so that the workgroup count fills whole rounds of the 256 CUs.  1: several launches are in flight on
  * different streams (rt.MultiLaneInference) -- a partial last round is filled by the other stream's workgroups, so

@@ -45,6 +45,8 @@ SOURCES = [
     ("wgrad.hip", NOSLP),
     ("stem_wgrad.hip", NOSLP),
     ("ingest.hip", ["-ffp-contract=off"]),
+    # augment.hip is bit-exact with a NumPy restatement: no contraction, and the normalisation's f32 divide IEEE-rounded
+    ("augment.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
 ]
 
 

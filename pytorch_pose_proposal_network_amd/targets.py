@@ -10,7 +10,7 @@ fields dataset.py:108-117 reads.  The encoder kernel (csrc/encode.hip) is bit-ex
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -42,7 +42,20 @@ def pack_people(batch: Sequence[Sequence[dict]], pmax: int = 0):
     return people, visible, count
 
 
-def encode_targets(packed, insize=(384, 384), outsize=(24, 24), local_grid=(21, 21), device="cuda") -> Dict[str, torch.Tensor]:
+def _to_device(a, dtype, dev):
+    """A device tensor is used as it is (no host copy); a NumPy array is uploaded."""
+    if isinstance(a, torch.Tensor):
+        if a.dtype != dtype or a.device.type != dev.type or not a.is_contiguous():
+            raise ValueError(f"packed tensors must be contiguous {dtype} tensors on {dev}, got {a.dtype} on {a.device}")
+        return a
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=str(dtype).split(".")[1])).to(dev)
+
+
+def encode_targets(packed, insize=(384, 384), outsize=(24, 24), local_grid=(21, 21), device="cuda",
+                   out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """packed = (people, visible, count) as pack_people returns them, or the same three arrays as device tensors (what
+    augment.augment_people writes: no host copy).  `out`: the dict of an earlier call with the same geometry, written again
+    instead of allocating eleven new tensors."""
     lib = L.load()
     people, visible, count = packed
     dev = torch.device(device)
@@ -53,18 +66,24 @@ def encode_targets(packed, insize=(384, 384), outsize=(24, 24), local_grid=(21, 
     c.sW, c.sH = local_grid
     c.W, c.H = outsize
     c.inW, c.inH = insize
-    pd = torch.from_numpy(np.ascontiguousarray(people)).to(dev)
-    vd = torch.from_numpy(np.ascontiguousarray(visible)).to(dev)
-    cd = torch.from_numpy(np.ascontiguousarray(count)).to(dev)
+    pd, vd, cd = _to_device(people, torch.float32, dev), _to_device(visible, torch.int32, dev), _to_device(count, torch.int32, dev)
+    limb_shape = (B, E, c.sH, c.sW, c.H, c.W)
     t = {}
     for k in TARGET_KEYS:
-        shape = (B, E, c.sH, c.sW, c.H, c.W) if k in ("weight_ij", "te") else (B, K, c.H, c.W)
-        t[k] = torch.empty(shape, dtype=torch.float32, device=dev)
+        shape = limb_shape if k in ("weight_ij", "te") else (B, K, c.H, c.W)
+        if out is not None:
+            if tuple(out[k].shape) != shape or out[k].dtype != torch.float32 or out[k].device.type != dev.type:
+                raise ValueError(f"out[{k!r}] does not fit this batch: {tuple(out[k].shape)} vs {shape}")
+            t[k] = out[k]
+        else:
+            t[k] = torch.empty(shape, dtype=torch.float32, device=dev)
     edges = (C.c_int32 * (2 * E))(*[int(v) for e in cfg.EDGES for v in e])
     # "limb_c" (u8, same shape as te): te | weight_ij in two bits per element -- what the two limb-streaming kernels of a
     # training iteration read instead of the two f32 tensors (PPNLoss.forward_backward_dz / limb_dual_nhwc use it when the
     # targets carry it; bit-identical results, 1.1 GB less HBM traffic per kernel at batch 32)
-    limb_c = torch.empty((B, E, c.sH, c.sW, c.H, c.W), dtype=torch.uint8, device=dev)
+    limb_c = out["limb_c"] if out is not None else torch.empty(limb_shape, dtype=torch.uint8, device=dev)
+    if tuple(limb_c.shape) != limb_shape or limb_c.dtype != torch.uint8:
+        raise ValueError("out['limb_c'] does not fit this batch")
     L.check(lib.ppn_encode_targets_c(C.byref(c), edges, pd.data_ptr(), vd.data_ptr(), cd.data_ptr(), B, pmax,
                                      *[t[k].data_ptr() for k in TARGET_KEYS], limb_c.data_ptr(), L.current_stream_ptr()),
             "ppn_encode_targets_c")
