@@ -305,6 +305,11 @@ typedef struct ppn_conv_desc {
     const void* stats_x;                       /* mode 2: the BatchNorm's input, NHWC like this launch's output */
     const float *stats_gamma, *stats_beta, *stats_mean, *stats_rstd;
     int32_t* stats_tiles;
+    /* Split-K workspace (flags & PPN_CONV_SPLIT_K, csrc/conv_splitk.hip): `splitk_ws_bytes` bytes of device memory, 16-byte
+     * aligned, at least what ppn_conv_splitk_workspace reports for this descriptor.  Scratch: every byte the launch reads it
+     * has written first, so the buffer needs no initialisation and one buffer may serve every launch of a stream in turn. */
+    void* splitk_ws;
+    int64_t splitk_ws_bytes;
 } ppn_conv_desc;
 #define PPN_CONV_NO_FILTER_BANK 1
 /* PPN_CONV_SHARED_GPU: this launch runs beside other streams' launches (rt.MultiLaneInference): the tile chooser then
@@ -319,6 +324,15 @@ typedef struct ppn_conv_desc {
  * half pairs -- the last launch of an exact (f32 + float16x3) PREFIX in front of a float16 trunk
  * (PoseProposalNet(compute_dtype="float16", exact_prefix=3): stem + layer3 exact, 251 of the reference's 260 people). */
 #define PPN_CONV_X3_PLAIN_OUT 8
+/* PPN_CONV_SPLIT_K: run this convolution as a split-K pair of launches (csrc/conv_splitk.hip) -- for launches whose
+ * pixels x channels fill a fraction of the GPU (batch 1-4 inference): the GEMM depth is cut into slabs of 512 values (a
+ * function of k_total alone), pixel tiles x channel tiles x slabs workgroups write f32 partial tiles to `splitk_ws` with plain
+ * stores, and a second launch sums them in slab order and applies the epilogue above.  Deterministic, and image i of a batch
+ * gets the bits it gets alone.  Scope: PPN_F32 / PPN_BF16 / PPN_F16, cin a multiple of the K step, ksize 1 or 3, NHWC outputs
+ * (PPN_CONV_OUT_BF16 included), whole-tensor launches, cout_pad a multiple of 64.  PPN_F16X3, src2, the NCHW head / arg-max /
+ * limb_edge_pad modes and stats_mode != 0 return PPN_E_UNSUPPORTED, a NULL or too small workspace PPN_E_INVALID; nothing is
+ * launched then and there is no fallback to the one-launch kernels.  The prefetch hint is ignored. */
+#define PPN_CONV_SPLIT_K 16
 
 /* GEMM-depth step / channel tile the packer must pad to for a conv of this shape and dtype, and the order of
  * the GEMM depth index in the packed weight rows:
@@ -332,6 +346,11 @@ int ppn_conv_tiling(int32_t dtype, int32_t cin, int32_t cout, int32_t ksize, int
                     int32_t* k_order);
 
 int ppn_conv2d_fused(const ppn_conv_desc* d, void* stream);
+
+/* Workspace of a PPN_CONV_SPLIT_K launch of this descriptor (pointers are not looked at; the flag need not be set):
+ * *bytes = slabs * batch * out_h * out_w * cout_pad * 4, *slabs = ceil(k_total / 512).  Returns what the launch would
+ * return for a descriptor outside the split-K scope.  Host only. */
+int ppn_conv_splitk_workspace(const ppn_conv_desc* d, int64_t* bytes, int32_t* slabs);
 
 /* One launch per 64-channel stride-1 pre-activation BasicBlock (drn.py:25-57; DRN-D's layer3 behind its first block), 16-bit
  * modes (csrc/block64.hip, round 5):

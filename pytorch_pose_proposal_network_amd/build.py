@@ -30,6 +30,7 @@ SOURCES = [
     ("decode.hip", ["-ffp-contract=off"]),
     ("conv.hip", NOSLP),
     ("conv_big.hip", NOSLP),
+    ("conv_splitk.hip", NOSLP),
     ("conv_head.hip", NOSLP),
     ("conv64.hip", NOSLP),
     ("block64.hip", NOSLP),

@@ -580,6 +580,7 @@ int conv_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname);
 int head_limb_launch(const ppn_conv_desc* d, long long m_lo, long long m_hi, hipStream_t st, const char** kname);
 bool conv64_supported(const ppn_conv_desc* d);
 int conv64_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname);
+int splitk_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname);   // conv_splitk.hip
 bool stem3x3_supported(int cin, int cout, int ksize, int stride, int dilation, int pad);
 int stem3x3_launch(int dtype, const void* src, int batch, int h, int w, int cout, int stride, const float* weight,
                    const float* scale1, const float* shift1, const float* scale2, const float* shift2, void* out_raw,
@@ -612,6 +613,8 @@ extern "C" int ppn_conv_tiling(int32_t dtype, int32_t cin, int32_t cout, int32_t
 
 int ppn::conv_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname) {
     if (!d) return ppn::fail(PPN_E_INVALID, "conv desc is NULL");
+    // opt-in split-K pair of launches (conv_splitk.hip): its own scope checks, never a fallback to the kernels below
+    if (d->flags & PPN_CONV_SPLIT_K) return ppn::splitk_launch(d, st, kname);
     if (d->stats_mode != 0) {
         // BatchNorm statistics from the epilogue: a request, not a demand -- *stats_tiles says whether this launch delivered
         if (d->stats_mode < 1 || d->stats_mode > 2 || !d->stats_partial || !d->stats_tiles)

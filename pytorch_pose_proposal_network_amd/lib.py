@@ -12,6 +12,7 @@ PPN_MAX_EDGES = 32
 PPN_MAX_KP = 32
 PPN_F32, PPN_BF16, PPN_F16, PPN_F16X3 = 0, 1, 2, 3
 PPN_CONV_NO_FILTER_BANK, PPN_CONV_SHARED_GPU, PPN_CONV_OUT_BF16, PPN_CONV_X3_PLAIN_OUT = 1, 2, 4, 8   # ppn_conv_desc.flags
+PPN_CONV_SPLIT_K = 16               # split-K pair of launches (csrc/conv_splitk.hip); needs ConvDesc.splitk_ws
 PPN_ACT_NONE, PPN_ACT_RELU, PPN_ACT_LRELU, PPN_ACT_SIGMOID = 0, 1, 2, 3
 PPN_STEM_RAW_S2 = 1 << 16           # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
 
@@ -52,6 +53,7 @@ class ConvDesc(C.Structure):
         ("stats_partial", C.c_void_p), ("stats_mode", C.c_int32), ("stats_act", C.c_int32), ("stats_x", C.c_void_p),
         ("stats_gamma", C.c_void_p), ("stats_beta", C.c_void_p), ("stats_mean", C.c_void_p), ("stats_rstd", C.c_void_p),
         ("stats_tiles", C.POINTER(C.c_int32)),
+        ("splitk_ws", C.c_void_p), ("splitk_ws_bytes", C.c_int64),
     ]
 
 
@@ -140,6 +142,7 @@ _SIGNATURES = {
     "ppn_conv_tiling": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ppn_conv2d_fused": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
+    "ppn_conv_splitk_workspace": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "ppn_set_conv64_enabled": (C.c_int, [C.c_int32]),
     "ppn_basicblock64_fused": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p]),
     "ppn_conv_split": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),

@@ -292,6 +292,50 @@ def block64_first(ops, oi: int, mode: Mode, table, s2_tensor) -> bool:
     return _block_tail_ok(mode, c1, c2, odt, table)
 
 
+# ---- low-latency plans (csrc/conv_splitk.hip) --------------------------------------------------------------------
+LATENCY = os.environ.get("PPN_LATENCY", "0") == "1"     # PPN_LATENCY=1: plans are built with latency=True unless told otherwise
+SPLITK_SLAB = 512                      # K values per slab (csrc/splitk_partition.h kSlabElems)
+SPLITK_MAX_WORKGROUPS = 64             # an ordinary launch of fewer workgroups fills less than a quarter of the 256 CUs
+SPLITK_MAX_BATCH = 4                   # latency plans are the batch 1-4 plans
+# Measured (profiles/latency_b1_parent.txt / latency_b1.txt: every in-scope launch under the size test alone, against the parent's launch
+# on the same box, batches 1 / 2 / 4; a class stays only if it gains >= 10 % at all three):
+#   16-bit modes: the 24 x 24 512-wide 3x3 layers (K = 4608, 50-55 us as one launch) -60 / -52 / -24 %; everything shallower
+#     (K <= 2304: 12-24 us launches at 48 x 48 and the neck's 128-wide 3x3) +0 .. +155 % -- two launches and the workspace
+#     round trip cost what the idle CUs would have saved.  So: K >= 4608.
+#   float32 (MFMA at the vector rate: the same layers take 75-290 us): every candidate -16 .. -83 %, except the 128 -> 256 3x3 at
+#     48 x 48 (K = 1152 over 36 ordinary workgroups per image: -0.4 % at batch 4).  So: K >= 1152 and at least 64 K values per
+#     ordinary workgroup of one image.
+SPLITK_MIN_K = {F32: 1152, BF16: 4608, F16: 4608}
+SPLITK_MIN_K_PER_WORKGROUP = 64
+
+
+def splitk_eligible(launch: "Launch") -> bool:
+    """Does a latency plan run this record as a split-K pair of launches?  A pure function of the record.
+
+    Scope of the kernel: a plain NHWC conv launch (no fused shortcut, NCHW head, arg-max, edge tile or pixel range) in
+    f32 / bf16 / f16, 3x3 or 1x1, cin a multiple of the K step, channel rows padded to the 64-channel tile.  Worth it: a
+    batch of at most SPLITK_MAX_BATCH, so few pixels x channels PER IMAGE that the ordinary launch of one frame -- whose
+    smallest tile is 128 pixels x 128 channels (64 below 128 channels) when there are fewer tiles than CUs -- would start
+    fewer than SPLITK_MAX_WORKGROUPS workgroups, and a GEMM depth the table above found to pay (SPLITK_MIN_K by dtype,
+    SPLITK_MIN_K_PER_WORKGROUP).  The size test looks at one image, not at the batch: the batch 1, 2 and 4 plans of a model
+    then split the SAME layers, so image i's head is bit for bit the one it gets alone (a split launch and the one-launch
+    kernel sum in different orders).  The block64 / stem / split / head records never qualify."""
+    if launch.kind != "conv":
+        return False
+    s, t = launch.scalars, launch.tensors
+    if s["dtype"] not in (F32, BF16, F16) or s["ksize"] not in (1, 3) or s["out_nchw_f32"] or s["batch"] > SPLITK_MAX_BATCH:
+        return False
+    if any(f in t for f in ("src2", "argmax_keys", "unary_out")) or s.get("limb_edge_pad") or s.get("m_count"):
+        return False
+    if s["cin"] % (32 if s["dtype"] == F32 else 64) or s["cout"] % 8 or s["cout_pad"] % 64:
+        return False
+    if s["k_total"] != s["ksize"] ** 2 * s["cin"] or s["k_total"] < max(2 * SPLITK_SLAB, SPLITK_MIN_K[s["dtype"]]):
+        return False
+    bc = 128 if s["cout"] >= 128 else 64
+    workgroups = -(-(s["out_h"] * s["out_w"]) // 128) * -(-s["cout"] // bc)
+    return workgroups < SPLITK_MAX_WORKGROUPS and s["k_total"] // workgroups >= SPLITK_MIN_K_PER_WORKGROUP
+
+
 # ---- launches ----------------------------------------------------------------------------------------------------
 @dataclass
 class Launch:
@@ -331,10 +375,11 @@ def _params(op, **fields):
 
 def lower(ops: List[A.ConvOp], mode: Mode, batch: int, h: int, w: int, src_is_u8: bool = True, fused: bool = False,
           conv_flags: int = 0, raw_s2: bool = True, prefetch: bool = True, head_edge: bool = True,
-          n_unary: int = 0, n_edges: int = 0, limb_window: int = 0) -> Lowered:
+          n_unary: int = 0, n_edges: int = 0, limb_window: int = 0, latency: bool = False) -> Lowered:
     """The plan of one input shape.  fused: the decode front end runs in the head conv (compact ``unary`` + arg-max
     ``keys`` instead of ``head``; the head is n_unary + n_edges * limb_window channels); conv_flags: ppn_conv_desc.flags of
-    every conv; raw_s2 / prefetch / head_edge: the plan-time knobs PPN_STEM_RAW_S2 / PPN_PREFETCH / PPN_HEAD_EDGE."""
+    every conv; raw_s2 / prefetch / head_edge: the plan-time knobs PPN_STEM_RAW_S2 / PPN_PREFETCH / PPN_HEAD_EDGE; latency: the
+    records ``splitk_eligible`` picks carry PPN_CONV_SPLIT_K (nothing else changes: same records, tensors and operands)."""
     shapes = A.tensor_shapes(ops, h, w)
     table, need_split, s2_tensor = tensor_table(ops, mode, batch, h, w, src_is_u8, raw_s2)
     if fused:
@@ -490,4 +535,8 @@ def lower(ops: List[A.ConvOp], mode: Mode, batch: int, h: int, w: int, src_is_u8
         launches.append(Launch("conv", op.name, flops, t, p, s))
         if odt == F32:
             add_splits(op)
+    if latency:
+        for l in launches:
+            if splitk_eligible(l):
+                l.scalars["flags"] |= L.PPN_CONV_SPLIT_K
     return Lowered(table, launches, A.conv_flops(ops, h, w) * batch)

@@ -51,8 +51,9 @@ def _arch_of(backbone) -> str:
 
 
 class _Plan:
-    def __init__(self, handle, buffers, head, entries, flops, input):
+    def __init__(self, handle, buffers, head, entries, flops, input, workspace=None):
         self.handle, self.buffers, self.head, self.flops = handle, buffers, head, flops
+        self.workspace = workspace      # the split-K scratch of a latency plan (one per plan, shared by its launches in turn)
         self.entries = entries          # [(name, flops)] aligned with the plan's launches
         self.n_ops = len(entries)
         self.input = input              # plan-owned input buffer: the captured hipGraph never depends on a caller's pointer
@@ -63,8 +64,11 @@ class PoseProposalNet:
                  keypoint_names=cfg.KEYPOINT_NAMES, local_grid_size=(21, 21), edges=cfg.EDGES,
                  compute_dtype: str = "float32", fuse_stem=None, fuse_shortcut: Optional[bool] = None,
                  stem_dtype: Optional[str] = None, half_prefix: Optional[int] = None, exact_prefix: int = -1,
-                 fuse_block: Optional[bool] = None):
+                 fuse_block: Optional[bool] = None, latency: Optional[bool] = None):
         self.arch = _arch_of(backbone)
+        # low-latency plans (batch 1-4): launches too small to fill the GPU run as split-K pairs (csrc/conv_splitk.hip,
+        # lowering.splitk_eligible); None: the PPN_LATENCY knob, off by default
+        self.latency = LW.LATENCY if latency is None else bool(latency)
         self.insize = insize
         self.outsize = outsize
         self.keypoint_names = keypoint_names
@@ -292,7 +296,8 @@ class PoseProposalNet:
         low = LW.lower(self._ops, self.mode, batch, h, w, src_is_u8, fused, conv_flags,
                        raw_s2=env.get("PPN_STEM_RAW_S2", "1") != "0", prefetch=env.get("PPN_PREFETCH", "1") != "0",
                        head_edge=env.get("PPN_HEAD_EDGE", "1") != "0", n_unary=6 * len(self.keypoint_names),
-                       n_edges=len(self.edges), limb_window=self.local_grid_size[0] * self.local_grid_size[1])
+                       n_edges=len(self.edges), limb_window=self.local_grid_size[0] * self.local_grid_size[1],
+                       **({"latency": True} if self.latency else {}))
         tensors = {}
         for name, (shape, st) in low.tensors.items():
             if name == "unary":
@@ -301,15 +306,25 @@ class PoseProposalNet:
                 # same-box round without it ran 0.7-2.6 % slower in every pair (profiles/ab_lowering_refactor.txt)
                 torch.empty(batch, self.lastsize, *shape[2:], dtype=torch.float32, device=self.device)
             tensors[name] = torch.empty(*shape, dtype=self._TORCH[st], device=self.device)
+        # ONE split-K workspace per plan, sized to the largest need among its flagged launches: the launches of a plan run
+        # one after the other on one stream, and each writes every byte it reads
+        need = 0
+        for launch in low.launches:
+            if launch.kind == "conv" and launch.scalars.get("flags", 0) & L.PPN_CONV_SPLIT_K:
+                nbytes = C.c_int64(0)
+                L.check(self._lib.ppn_conv_splitk_workspace(C.byref(L.ConvDesc(**launch.scalars)), C.byref(nbytes), None),
+                        f"ppn_conv_splitk_workspace({launch.name})")
+                need = max(need, nbytes.value)
+        workspace = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
         handle = C.c_void_p()
         L.check(self._lib.ppn_plan_create(C.byref(handle)), "ppn_plan_create")
         for launch in low.launches:
-            L.check(self._emit(handle, launch, tensors), f"ppn_plan_add_{launch.kind}({launch.name})")
+            L.check(self._emit(handle, launch, tensors, workspace), f"ppn_plan_add_{launch.kind}({launch.name})")
         bufs = {k: t for k, t in tensors.items() if k != "input"}
         head = (bufs["unary"], bufs["keys"]) if fused else bufs["head"]
-        return _Plan(handle, bufs, head, low.entries, low.flops, tensors["input"])
+        return _Plan(handle, bufs, head, low.entries, low.flops, tensors["input"], workspace)
 
-    def _emit(self, handle, launch: LW.Launch, tensors) -> int:
+    def _emit(self, handle, launch: LW.Launch, tensors, workspace=None) -> int:
         """One ppn_plan_add_* call: the record's tensor names become buffer pointers, its parameter keys `_dev` pointers
         (a key `_dev` does not hold: NULL)."""
         lib, s = self._lib, launch.scalars
@@ -320,6 +335,8 @@ class PoseProposalNet:
             pf = self._dev.get(launch.params.get("prefetch"))
             if pf is not None:
                 d.prefetch_bytes = pf.numel() * pf.element_size()
+            if launch.kind == "conv" and s.get("flags", 0) & L.PPN_CONV_SPLIT_K:
+                d.splitk_ws, d.splitk_ws_bytes = workspace.data_ptr(), workspace.numel()
             return (lib.ppn_plan_add_conv if launch.kind == "conv" else lib.ppn_plan_add_block)(handle, C.byref(d))
         if launch.kind == "split":
             return lib.ppn_plan_add_split(handle, t["src"], s["rows"], s["channels"], t["dst"])

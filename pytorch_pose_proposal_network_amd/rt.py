@@ -24,15 +24,16 @@ from .model import PoseProposalNet
 
 
 def network(resume: Optional[str] = None, image_size: int = 384, arch: str = "drn_d_22",
-            compute_dtype: str = "float32", state_dict=None):
+            compute_dtype: str = "float32", state_dict=None, latency: Optional[bool] = None):
     """rt_test.py:52-85: build D-22 PPN, derive ``outsize`` and load ``checkpoint['state_dict']``.
 
     The reference discovers ``outsize`` with a dummy forward (rt_test.py:65-68); the network is fully
-    convolutional with total stride 16, so it is ``image_size // 16`` here."""
+    convolutional with total stride 16, so it is ``image_size // 16`` here.  ``latency=True``: low-latency plans for the
+    reference's one-frame-at-a-time use (PoseProposalNet(latency=True); None: the PPN_LATENCY knob)."""
     local_grid_size = (21, 21)
     outsize = (image_size // 16, image_size // 16)
     model = PoseProposalNet(getattr(drn, arch)(), insize=(image_size, image_size), outsize=outsize,
-                            local_grid_size=local_grid_size, compute_dtype=compute_dtype).cuda()
+                            local_grid_size=local_grid_size, compute_dtype=compute_dtype, latency=latency).cuda()
     if resume is not None:
         ckpt = torch.load(resume, map_location="cpu")
         state_dict = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
