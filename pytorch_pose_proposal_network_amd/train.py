@@ -580,6 +580,15 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, in_hw, stride: int = 1, dilati
     cout, cin, k, _ = w.shape
     eff = dilation * (k - 1) + 1
     B, Ho, Wo, _ = dy.shape
+    # The convolution kernels reduce over dy's channels in K steps and take a channel count that is a multiple of the step or a
+    # power of two below it: any other cout (72) gets zero channels up to the next multiple -- they add exact zeros to the f32 sums
+    # (no layer of the networks is one: the first test keeps the library call off their path)
+    if cout % 64 and cout & (cout - 1):
+        grow = -cout % L.conv_tiling(_dtype_code(dy), cout, cin, k)[0]
+        if grow:
+            dy = torch.nn.functional.pad(dy, (0, grow))
+            w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, grow))
+            cout += grow
     # measured at batch 32 (tools/bench_dgrad_s2.py, bit-identical results): 1x1 projections 119 -> 51 and 74 -> 37 us,
     # layer2 (16 -> 32) 402 -> 359 us; the 3x3 layers with >= 32 input channels do not gain (181 -> 187, 106 -> 130 us:
     # four short-K launches and four strided copies cost what the 2.25x fewer FLOPs save) and keep the zero-upsampled form

@@ -146,12 +146,17 @@ def test_bf16_gradients_track_f32():
     tensors of the exact f32 pipeline to bf16 (weights, conv outputs, BN outputs) already turns the gradients by
     cos 0.89 (stem) .. 0.999 (conv3) -- rounding the backward tensors changes nothing (cos 1.0000, measured).  The bf16
     kernels must do no worse than that emulation by more than a small margin, tensor by tensor."""
-    from pytorch_pose_proposal_network_amd import lib as L, train as T
-    from pytorch_pose_proposal_network_amd.trainer import PPNTrainer
     g, sd, x, tg, size = _setup()
     dev = torch.device("cuda")
     xd = torch.as_tensor(x).to(dev)
     tgd = {k: torch.from_numpy(v).to(dev) for k, v in tg.items()}
+    _check_bf16_gradients_track_f32(sd, xd, tgd, (size, size))
+
+
+def _check_bf16_gradients_track_f32(sd, xd, tgd, insize):
+    """The criterion of test_bf16_gradients_track_f32 on a given input (insize as PPNTrainer takes it)."""
+    from pytorch_pose_proposal_network_amd import lib as L, train as T
+    from pytorch_pose_proposal_network_amd.trainer import PPNTrainer
     orig_conv, orig_bnf = T.conv2d_nhwc, T.bn_train_forward
 
     def rb(t):
@@ -172,7 +177,7 @@ def test_bf16_gradients_track_f32():
 
         T.conv2d_nhwc, T.bn_train_forward = convf, bnf
         try:
-            tr = PPNTrainer("drn_d_22", sd, compute_dtype=dt, insize=(size, size))
+            tr = PPNTrainer("drn_d_22", sd, compute_dtype=dt, insize=insize)
             head = tr.forward(xd)
             _, gh = tr.criterion.forward_backward(head, tgd, coeff=[0.2] * 5)
             tr.backward(gh)
