@@ -484,6 +484,15 @@ int ppn_set_conv64_enabled(int32_t on);
  * (e.g. "conv_igemm_big_kernel<__bf16, 192, 256, 8, false>"); "" before the first call. */
 const char* ppn_last_conv_kernel(void);
 
+/* Strip loader of the large-tile kernel's 192 x 256 tile (csrc/conv_big.hip, template flag SP): 3x3 stride-1 "same"
+ * convolutions of the 16-bit modes whose 192-pixel tiles are whole image rows stage one activation strip per filter row
+ * instead of one stage per tap; results are bit-identical (tests/test_conv_strip_gpu.py).  ppn_last_conv_kernel() reports
+ * the tile's name either way; ppn_last_conv_strip() is 1 iff the calling thread's last successful ppn_conv2d_fused took
+ * the strip loader.  ppn_set_conv_strip_enabled: process-wide switch for every later launch and plan run (test and A/B
+ * hook); initial value 1 unless PPN_CONV_STRIP=0 is in the environment. */
+int ppn_last_conv_strip(void);
+int ppn_set_conv_strip_enabled(int32_t on);
+
 /*
  * First layer (drn.py:123-128 layer0: 7x7 conv 3->16, BN, ReLU) with the input normalisation of
  * rt_test.py:97-101 / aug.py:149-153 fused into the load.

@@ -771,6 +771,7 @@ int ppn::conv_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname)
     a.out_bf16 = (d->flags & PPN_CONV_OUT_BF16) ? 1 : 0;
     a.st_partial = nullptr; a.st_mode = 0; a.st_act = 0; a.st_x = nullptr;
     a.st_gamma = a.st_beta = a.st_mean = a.st_rstd = nullptr;
+    a.sp_rows = a.sp_pitch = 0; a.sp_div = make_fastdiv(1);          // set by launch_big
     if (d->stats_mode != 0 && big && big_stats_ok(d->dtype, bt) && !d->out_nchw_f32 && !d->residual && !d->out_act && d->out_raw &&
         d->cout % 8 == 0 && !a.out_bf16 && !d->src2 && !d->argmax_keys && d->m_count == 0 && a.n_ptiles <= 1024) {
         // the conditions of the single-output 16-bit epilogue (conv_big.hip `fast`) + one launch over the whole tensor +
@@ -803,15 +804,20 @@ extern "C" int ppn_conv_split(int32_t dtype, int32_t cin, int32_t cout, int64_t 
 }
 
 static thread_local const char* g_last_conv_kernel = "";
+static thread_local int g_last_conv_strip = 0;
 
 extern "C" int ppn_conv2d_fused(const ppn_conv_desc* d, void* stream) {
     const char* kn = nullptr;
+    ppnconv::g_last_strip = 0;
     const int rc = ppn::conv_launch(d, static_cast<hipStream_t>(stream), &kn);
     if (rc == PPN_OK && kn) g_last_conv_kernel = kn;
+    g_last_conv_strip = rc == PPN_OK ? ppnconv::g_last_strip : g_last_conv_strip;
     return rc;
 }
 
 extern "C" const char* ppn_last_conv_kernel(void) { return g_last_conv_kernel; }
+
+extern "C" int ppn_last_conv_strip(void) { return g_last_conv_strip; }
 
 static int pack_weight_impl(int32_t dtype, const float* w, int32_t cout, int32_t cin, int32_t ksize,
                             int32_t cout_pad, int32_t k_total, int32_t k_order, int32_t k_step, void* out,

@@ -120,11 +120,25 @@ __device__ __forceinline__ void bufload_lds16(__amdgpu_buffer_rsrc_t rsrc, char*
 // (ppn_conv_desc.stats_mode); its own instantiations, so the inference kernels are the code they were.
 // (the 192 x 128 tile runs two workgroups per CU = four waves per SIMD at 126 VGPRs; its ST twin came out at 129, i.e. ONE
 // workgroup per CU, so that instantiation states the four waves it needs)
-template <typename T, int BP, int BC, int NW, bool SC, bool X3 = false, bool ST = false>
+// SP: strip loader of the 3x3 stride-1 launches whose 192-pixel tiles are whole image rows (strip_eligible() below).  Within a
+// 64-channel slab the K order is dx innermost, and the activation stages of taps (dy, 0), (dy, 1), (dy, 2) hold the same
+// pixels shifted by `dil` columns: instead of one stage per tap, ONE strip of R image rows x P columns (P = Wo + margins,
+// a.sp_rows x a.sp_pitch) is staged per filter row (slab, dy) and tap dx reads it shifted by dx * dil strip rows.
+//   LDS     2 strip buffers x 256 rows x 128 B, alternating per filter row, + the 2 weight stages = 128 KiB
+//   loads   the strip of filter row q+1 is requested during the three steps of row q (2 + 1 + 1 pieces per wave) beside each
+//           step's weights; every step still ends with vmcnt(0) + barrier, and the buffer being refilled was last read
+//           before the previous row's closing barrier
+//   swizzle key (row & 6) on the 16-byte chunk index, on the source address and on the read: conflict-free for ANY 16
+//           consecutive rows (the old key (row >> 1) & 7 is 2-way conflicted for shifts that are no multiple of 4); where
+//           16-pixel MFMA tiles straddle image rows (Wo = 24), P = Wo (mod 8) keeps row % 8 running on
+// Same weights, K order, MFMA sequence and epilogues: results are bit-identical.  The K loop is unrolled over dx, so the nine
+// fragment offsets per lane (pixel tile x dx) and the strip pieces of a step are compile-time choices.
+template <typename T, int BP, int BC, int NW, bool SC, bool X3 = false, bool ST = false, bool SP = false>
 __global__ void __launch_bounds__(64 * NW, (ST && BP == 192 && BC == 128) ? 4 : NW / 4)
 conv_igemm_big_kernel(ConvKArgs a, unsigned src_bytes, unsigned wgt_bytes) {
     static_assert(!X3 || (std::is_same<T, _Float16>::value && !SC), "X3 is the split-f16 mode without a fused shortcut");
     static_assert(!ST || (sizeof(T) == 2 && !SC && !X3 && NW == 8 && BC >= 128), "ST: plain 16-bit launches of the 8-wave tiles");
+    static_assert(!SP || (sizeof(T) == 2 && BP == 192 && BC == 256 && NW == 8 && !SC && !X3 && !ST), "SP: the plain 16-bit 192 x 256 tile");
     constexpr int EPC = Elem<T>::EPC;
     constexpr int BK = 8 * EPC;
     constexpr int ES = sizeof(T);
@@ -207,6 +221,43 @@ conv_igemm_big_kernel(ConvKArgs a, unsigned src_bytes, unsigned wgt_bytes) {
         woff[j] = (unsigned)(((size_t)(c0 + row) * a.Ktot + chunk * EPC) * ES);
     }
 
+    // ---- SP: strip loader state.  Piece p of a wave covers strip rows (p * NW + wave) * 8 + lrow; strip row sr = r * P + col
+    // is image row oy0 + r (+ (dy - 1) * dil), column col - dil.  LDS chunk position lane & 7 of row sr holds source chunk
+    // (lane & 7) ^ (sr & 6), and sr & 6 == lrow & 6 for every piece.
+    constexpr int SBUF = 256 * 128;                                  // one strip buffer
+    constexpr int NSP = 4;                                           // strip pieces per wave and filter row (256 rows / 8 / NW)
+    int sbase[NSP];          // byte offset of (strip row, dy 0, ci 0, this lane's chunk); may be negative
+    unsigned smask = 0;      // bit 3 * p + dy: strip row of piece p exists in the image for filter row dy (a piece past the
+                             // strip's R * P rows is requested all the same: zero fill inside the buffer, no memory traffic)
+    int xoff[TP][3];         // fragment read offsets inside a strip buffer per (pixel tile, dx)
+    if constexpr (SP) {
+        const int P = a.sp_pitch;
+        const int schunk = (lane & 7) ^ (lrow & 6);
+        const int b0 = fast_div(m0, a.div_howo), oy0 = fast_div(m0 - b0 * a.HoWo, a.div_wo);
+#pragma unroll
+        for (int p = 0; p < NSP; ++p) {
+            const int sr = (p * NW + wave) * 8 + lrow;
+            const int r = fast_div(sr, a.sp_div), col = sr - r * P;
+            const int iy0 = oy0 + r - a.dil, ix = col - a.dil;
+            sbase[p] = (((b0 * a.H + iy0) * a.W + ix) * a.Cin + schunk * EPC) * ES;
+            const bool colok = r < a.sp_rows && (unsigned)ix < (unsigned)a.W;
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy)
+                smask |= (colok && (unsigned)(iy0 + dy * a.dil) < (unsigned)a.H) ? (1u << (3 * p + dy)) : 0u;
+        }
+        const int fr = lane & 15, fqq = lane >> 4;
+#pragma unroll
+        for (int j = 0; j < TP; ++j) {
+            const int ml = wp * (BP / WP) + j * 16 + fr;
+            const int r = fast_div(ml, a.div_wo), rb = r * P + (ml - r * a.Wo);
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const int row = rb + dx * a.dil;
+                xoff[j][dx] = row * 128 + ((fqq ^ (row & 6)) << 4);
+            }
+        }
+    }
+
     const int nsteps = a.Ktot / BK;
     // Wave-uniform K iteration state, advanced incrementally so the loop keeps only a handful of SGPRs live
     // (depth order 1 of ppn_conv_tiling: taps innermost, then the next BK-channel slab).
@@ -272,6 +323,35 @@ conv_igemm_big_kernel(ConvKArgs a, unsigned src_bytes, unsigned wgt_bytes) {
         }
     };
     constexpr int NL = NXI + NWI;                                    // LDS-DMA instructions per stage and thread
+    // SP: wave-uniform state of the filter row being LOADED (slab, dy) and of the weight step being loaded
+    const int sp_dy_bytes = a.dil * a.W * a.Cin * ES;               // one filter row down
+    const int sp_nq = nsteps / 3;                                    // filter rows = 3 * slabs
+    int sp_row = 0, sp_dy = 0, sp_slab = 0, sp_off = 0;
+    unsigned sp_bit = 1u;                                            // 0 once past the last filter row
+    auto sp_advance_row = [&]() {
+        ++sp_row; ++sp_dy;
+        sp_off += sp_dy_bytes;
+        const bool wrap = sp_dy == 3;
+        sp_dy = wrap ? 0 : sp_dy;
+        sp_slab += wrap ? BK * ES : 0;
+        sp_off = wrap ? sp_slab : sp_off;
+        sp_bit = sp_row < sp_nq ? (1u << sp_dy) : 0u;
+    };
+    auto sp_advance_w = [&]() {
+        ++ld_step;
+        live = ld_step < nsteps;
+        ksoff = live ? ksoff + BK * ES : 0u;
+    };
+    // piece p of the strip being loaded -> strip buffer at byte offset sb
+    auto sp_issue_strip = [&](auto pc, int sb) {
+        constexpr int p = decltype(pc)::value;
+        const unsigned voff = ((smask >> (3 * p)) & sp_bit) ? (unsigned)(sbase[p] + sp_off) : kOOB;
+        bufload_lds16(xrs, smem + sb + (p * NW + wave) * 1024, voff, 0);
+    };
+    auto sp_issue_w = [&](auto jc, int buf) {
+        constexpr int j = decltype(jc)::value;
+        bufload_lds16(wrs, smem + 2 * SBUF + buf * (BC * 128) + (j * NW + wave) * 1024, live ? woff[j] : kOOB, ksoff);
+    };
 
     const int frow = lane & 15, fq = lane >> 4;
     const int fswz = (frow >> 1) & 7;
@@ -299,6 +379,17 @@ conv_igemm_big_kernel(ConvKArgs a, unsigned src_bytes, unsigned wgt_bytes) {
             xf[r] = *reinterpret_cast<const f32x4*>(smem + buf * STAGE + x_tile_off + foff[ks] + r * 16 * 128);
         else
             wf[r - TP] = *reinterpret_cast<const f32x4*>(smem + buf * STAGE + w_tile_off + foff[ks] + (r - TP) * 16 * 128);
+    };
+    // SP: activation fragments from the strip buffer at xsel = buffer offset | ks * 64 (both are single bits above / below
+    // every xoff, and the swizzle key never touches chunk bit 2, so the OR is an XOR), weights as above
+    auto sp_read_one = [&](auto rc, auto dxc, f32x4 (&wf)[TC], f32x4 (&xf)[TP], int wbuf, int xsel, int ks) {
+        constexpr int r = decltype(rc)::value;
+        constexpr int DX = decltype(dxc)::value;
+        if constexpr (r < TP)
+            xf[r] = *reinterpret_cast<const f32x4*>(smem + (xoff[r][DX] ^ xsel));
+        else
+            wf[r - TP] = *reinterpret_cast<const f32x4*>(smem + 2 * SBUF + wbuf * (BC * 128) + wc * (BC / WC) * 128 + foff[ks] +
+                                                         (r - TP) * 16 * 128);
     };
     // MFMA group: GS consecutive output tiles of the wave (flat index = i*TP + j); 4 wherever the tile count allows
     constexpr int GS = (TC * TP % 4 == 0) ? 4 : ((TC * TP % 3 == 0) ? 3 : 2);
@@ -337,23 +428,41 @@ conv_igemm_big_kernel(ConvKArgs a, unsigned src_bytes, unsigned wgt_bytes) {
 #endif
     // Both stages are requested before the first wait, so their (cold) fill latencies overlap; LDS-DMA completes
     // in issue order, so "all but the NL youngest" means stage 0 has landed.
-    static_for<NL>([&](auto gc) { issue_one(gc, 0); });
-    advance();
-    static_for<NL>([&](auto gc) { issue_one(gc, 1); });
-    advance();
-    if constexpr (XRAGGED) {
-        // waves whose last activation piece lies past the tile issued one DMA fewer per stage
-        if ((NXI - 1) * NW * 8 + wave * 8 < BP) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL - 1) : "memory");
+    if constexpr (SP) {
+        // filter row 0 whole + the weights of step 0; then the weights of step 1 + the first share of filter row 1
+        static_for<NSP>([&](auto pc) { sp_issue_strip(pc, 0); });
+        static_for<NWI>([&](auto jc) { sp_issue_w(jc, 0); });
+        sp_advance_row();
+        sp_advance_w();
+        static_for<2>([&](auto pc) { sp_issue_strip(pc, SBUF); });
+        static_for<NWI>([&](auto jc) { sp_issue_w(jc, 1); });
+        sp_advance_w();
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWI + 2) : "memory");
     } else {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");
+        static_for<NL>([&](auto gc) { issue_one(gc, 0); });
+        advance();
+        static_for<NL>([&](auto gc) { issue_one(gc, 1); });
+        advance();
+        if constexpr (XRAGGED) {
+            // waves whose last activation piece lies past the tile issued one DMA fewer per stage
+            if ((NXI - 1) * NW * 8 + wave * 8 < BP) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL - 1) : "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");
+        }
     }
     __syncthreads();
 #ifdef PPN_CLOCK
     const unsigned long long ck_bar = __builtin_amdgcn_s_memtime();
 #endif
-    static_for<NRD>([&](auto rc) { read_one(rc, wA, xA, 0, 0); });
-    static_for<NRD>([&](auto rc) { read_one(rc, wB, xB, 0, 1); });
+    if constexpr (SP) {
+        constexpr std::integral_constant<int, 0> dx0{};
+        static_for<NRD>([&](auto rc) { sp_read_one(rc, dx0, wA, xA, 0, 0, 0); });
+        static_for<NRD>([&](auto rc) { sp_read_one(rc, dx0, wB, xB, 0, 64, 1); });
+    } else {
+        static_for<NRD>([&](auto rc) { read_one(rc, wA, xA, 0, 0); });
+        static_for<NRD>([&](auto rc) { read_one(rc, wB, xB, 0, 1); });
+    }
     static_for<NG>([&](auto gc) { mma_group(gc, wA, xA); });
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
@@ -373,7 +482,54 @@ conv_igemm_big_kernel(ConvKArgs a, unsigned src_bytes, unsigned wgt_bytes) {
     // in-kernel clock: shader cycles (s_memtime) over the 100 MHz constant clock (s_memrealtime) around the K loop
     const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rk0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    for (int s = 1; s < nsteps; ++s) {
+    if constexpr (SP) {
+        // The same step, unrolled over dx: step s = 3 * q + DX reads strip buffer q & 1 (byte offset sbo) shifted by DX * dil rows
+        // and weight stage s & 1; it requests the weights of step s + 1 and share DX of the strip of filter row q + 1 (pieces
+        // 0 and 1, 2, 3) into the other strip buffer, one DMA per MFMA group.
+        int s = 1, sbo = 0;
+        auto step = [&](auto dxc) {
+            constexpr int DX = decltype(dxc)::value;
+            constexpr int NS = DX == 0 ? 2 : 1;                          // strip pieces of this step
+            const int buf = s & 1;
+            static_for<NG>([&](auto gc) {
+                constexpr int g = decltype(gc)::value;
+                mma_group(gc, wB, xB);
+                if constexpr (g < NS) sp_issue_strip(std::integral_constant<int, (DX == 0 ? g : DX + 1)>{}, sbo ^ SBUF);
+                else if constexpr (g < NS + NWI) sp_issue_w(std::integral_constant<int, g - NS>{}, buf ^ 1);
+                static_for<RPG>([&](auto rc) {
+                    constexpr int r = g * RPG + decltype(rc)::value;
+                    if constexpr (r < NRD) sp_read_one(std::integral_constant<int, r>{}, dxc, wA, xA, buf, sbo, 0);
+                });
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            sp_advance_w();
+            static_for<NG>([&](auto gc) {
+                constexpr int g = decltype(gc)::value;
+                mma_group(gc, wA, xA);
+                static_for<RPG>([&](auto rc) {
+                    constexpr int r = g * RPG + decltype(rc)::value;
+                    if constexpr (r < NRD) sp_read_one(std::integral_constant<int, r>{}, dxc, wB, xB, buf, sbo | 64, 1);
+                });
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __syncthreads();
+            ++s;
+        };
+        static_assert(NG >= 2 + NWI, "one DMA per MFMA group");
+        // (the last filter row is peeled so that the loop leaves at its end: with the exit between two steps the register
+        // allocator no longer kept the accumulators in place and spilled)
+        for (int q = 1; q < sp_nq; ++q) {
+            step(std::integral_constant<int, 1>{});
+            step(std::integral_constant<int, 2>{});
+            sbo ^= SBUF;
+            sp_advance_row();
+            step(std::integral_constant<int, 0>{});
+        }
+        step(std::integral_constant<int, 1>{});
+        step(std::integral_constant<int, 2>{});
+    } else
+    for (int s = 1; s < nsteps; ++s) {                               // (not indented: the loop every other instantiation always had)
         const int buf = s & 1;
 #ifdef PPN_STAMP
         PPN_T(tq0);
@@ -947,9 +1103,10 @@ conv_igemm_big_kernel(ConvKArgs a, unsigned src_bytes, unsigned wgt_bytes) {
 #endif
 }
 
-template <typename T, int BP, int BC, int NW, bool SC, bool X3 = false, bool ST = false>
+template <typename T, int BP, int BC, int NW, bool SC, bool X3 = false, bool ST = false, bool SP = false>
 int launch_sc(const ConvKArgs& a, hipStream_t st, const char** kname) {
-    constexpr size_t lds = 2 * (size_t)(BP + BC) * 128;
+    // SP: two 256-row strip buffers instead of the two activation stages; the reported name stays the tile's
+    constexpr size_t lds = SP ? 2 * (size_t)(256 + BC) * 128 : 2 * (size_t)(BP + BC) * 128;
     static char name[96];
     if (!name[0])
         snprintf(name, sizeof(name), "conv_igemm_big_kernel<%s, %d, %d, %d, %s%s>", elem_name<T>(),
@@ -957,7 +1114,7 @@ int launch_sc(const ConvKArgs& a, hipStream_t st, const char** kname) {
     if (kname) *kname = name;
     const size_t src_bytes = (size_t)a.B * a.H * a.W * a.Cin * sizeof(T);
     const size_t wgt_bytes = (size_t)a.n_ctiles * BC * a.Ktot * sizeof(T);
-    auto k = conv_igemm_big_kernel<T, BP, BC, NW, SC, X3, ST>;
+    auto k = conv_igemm_big_kernel<T, BP, BC, NW, SC, X3, ST, SP>;
     {
         static int max_lds_set = 0;   // the attribute sticks to the function: set it when it grows
         PPN_LDS_ONCE(max_lds_set, reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -986,6 +1143,9 @@ int launch_one(const ConvKArgs& a, hipStream_t st, const char** kname) {
             return launch_sc<T, BP, BC, NW, false, false, true>(a, st, kname);
         else
             return ppn::fail(PPN_E_UNSUPPORTED, "BatchNorm statistics: no such instantiation of the large-tile kernel");
+    }
+    if constexpr (sizeof(T) == 2 && BP == 192 && BC == 256 && NW == 8) {
+        if (a.sp_rows > 0) return launch_sc<T, BP, BC, NW, false, false, false, true>(a, st, kname);
     }
     return launch_sc<T, BP, BC, NW, false>(a, st, kname);
 }
@@ -1171,6 +1331,25 @@ bool big_stats_ok(int dtype, BigTile t) {
     return dtype == PPN_BF16 && conv_waves() == 8 && stats_tile_ok(t.bp, t.bc);
 }
 
+// Strip loader (kernel flag SP): on (1) / off (0) for every later launch and plan run; -1 = not yet read from PPN_CONV_STRIP
+static int g_strip_on = -1;
+thread_local int g_last_strip = 0;
+
+// Does this launch take the strip loader?  3x3, stride 1, "same" padding on the 192 x 256 tile of a 16-bit mode, plain
+// NHWC epilogues, and every tile R = 192 / Wo whole rows of one image; the strip of R rows at pitch P = Wo + margins
+// (P = Wo (mod 8), room for 2 * dil columns of padding) must fit the 256-row buffer.
+static bool strip_eligible(const ConvKArgs& a, int dtype, BigTile t, int* rows, int* pitch) {
+    if (g_strip_on < 0) g_strip_on = (getenv("PPN_CONV_STRIP") && atoi(getenv("PPN_CONV_STRIP")) == 0) ? 0 : 1;
+    if (!g_strip_on || conv_waves() != 8 || t.bp != 192 || t.bc != 256 || (dtype != PPN_BF16 && dtype != PPN_F16)) return false;
+    if (a.ks != 3 || a.stride != 1 || a.dil < 1 || a.pad != a.dil || a.Ho != a.H || a.Wo != a.W || a.Ktot != 9 * a.Cin) return false;
+    if (a.src2 || a.st_mode != 0 || a.nchw || a.amax_keys || a.unary_out) return false;
+    if (192 % a.Wo != 0 || a.HoWo % 192 != 0 || a.m_base % 192 != 0 || (a.M - a.m_base) % 192 != 0) return false;
+    const int r = 192 / a.Wo, p = a.Wo + 8 * ((2 * a.dil + 7) / 8);
+    if (r * p > 256) return false;
+    *rows = r; *pitch = p;
+    return true;
+}
+
 int launch_big(const ConvKArgs& a, int dtype, BigTile t, hipStream_t st, const char** kname) {
     // buffer descriptors address up to 2 GiB with the out-of-range marker used for padding
     const size_t es = dtype == PPN_F32 ? 4 : 2;
@@ -1178,8 +1357,13 @@ int launch_big(const ConvKArgs& a, int dtype, BigTile t, hipStream_t st, const c
         return ppn::fail(PPN_E_UNSUPPORTED, "tensor too large for the buffer-addressed conv kernel");
     if (dtype == PPN_F32) return launch_T<float>(a, t, st, kname);
     if (dtype == PPN_F16X3) return launch_X3(a, t, st, kname);
-    if (dtype == PPN_F16) return launch_T<_Float16>(a, t, st, kname);
-    return launch_T<__bf16>(a, t, st, kname);
+    ConvKArgs b = a;
+    b.sp_rows = b.sp_pitch = 0;
+    b.sp_div = make_fastdiv(1);
+    if (strip_eligible(a, dtype, t, &b.sp_rows, &b.sp_pitch)) b.sp_div = make_fastdiv((unsigned)b.sp_pitch);
+    const int rc = dtype == PPN_F16 ? launch_T<_Float16>(b, t, st, kname) : launch_T<__bf16>(b, t, st, kname);
+    if (rc == PPN_OK) g_last_strip = b.sp_rows > 0 ? 1 : 0;
+    return rc;
 }
 
 }  // namespace ppnconv
@@ -1189,6 +1373,11 @@ extern "C" int ppn_set_conv_tile_override(int32_t bp, int32_t bc) {
     if (!ppnconv::tile_shape_ok(bp, bc))
         return ppn::fail(PPN_E_INVALID, "ppn_set_conv_tile_override: bp in {128,192,256}, bc in {64,128,256}, not 192x64; or 144x256");
     ppnconv::g_ov_bp = bp; ppnconv::g_ov_bc = bc;
+    return PPN_OK;
+}
+
+extern "C" int ppn_set_conv_strip_enabled(int32_t on) {
+    ppnconv::g_strip_on = on ? 1 : 0;
     return PPN_OK;
 }
 

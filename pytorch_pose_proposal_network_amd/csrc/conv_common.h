@@ -67,6 +67,10 @@ struct ConvKArgs {
     int st_mode, st_act;
     const char* st_x;
     const float *st_gamma, *st_beta, *st_mean, *st_rstd;
+    // strip loader of the large-tile kernel (SP instantiations; set by launch_big): image rows per 192-pixel tile (0 = off),
+    // strip pitch in pixels and the divider by it
+    int sp_rows, sp_pitch;
+    FastDiv sp_div;
 };
 
 template <typename T>
@@ -204,6 +208,7 @@ bool big_tile_for(int cout, long long m, BigTile* out, int ksteps = 0, bool shar
 // tile, the rest a smaller tile that fills one more round (conv_big.hip).
 long long big_split_for(int cout, long long m);
 int launch_big(const ConvKArgs& a, int dtype, BigTile t, hipStream_t st, const char** kname);
+extern thread_local int g_last_strip;       // the calling thread's last large-tile launch took the strip loader (conv_big.hip)
 bool big_stats_ok(int dtype, BigTile t);   // the tile has the BatchNorm-statistics epilogue (ppn_conv_desc.stats_mode)
 
 }  // namespace ppnconv

@@ -201,6 +201,8 @@ _SIGNATURES.update({
     "ppn_set_conv_tile_policy": (C.c_int, [C.c_int32]),
     "ppn_set_conv_tile_override": (C.c_int, [C.c_int32, C.c_int32]),
     "ppn_last_conv_kernel": (C.c_char_p, []),
+    "ppn_last_conv_strip": (C.c_int, []),
+    "ppn_set_conv_strip_enabled": (C.c_int, [C.c_int32]),
     "ppn_add_relu": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ppn_relu_mask": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ppn_upsample_zero": (C.c_int, [C.c_int32, C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_void_p]),
