@@ -459,6 +459,64 @@ int ppn_augment_people(const float* people, const int32_t* visible, const int32_
                        int32_t pmax, int32_t K, int32_t out_h, int32_t out_w, float* people_out, int32_t* visible_out,
                        int32_t* count_out, void* stream);
 
+/*
+ * Drawing the decoded people on the device (datatest.py:162-232, draw_humans), csrc/render.hip: a tiled rasteriser over
+ * the compact decode result that paints exactly the pixels PIL's ImageDraw paints for the reference's calls (established
+ * against Pillow 12.2; tests/render_ref.py restates the rules below in NumPy, tests/golden/draw_cases.npz holds frames the
+ * reference itself drew).  All f32 arithmetic is in the written order, uncontracted, with IEEE division.
+ *
+ * Paint order: people 0 .. min(count, max_humans) - 1 in order; within a person the keypoints kp_order[0 .. K-1] that are
+ * present (kp_cell >= 0), then the limbs e = 0 .. E-1 whose two ends are present; a later primitive overwrites an earlier
+ * one.  T(v) is truncation toward zero of an f32, midpoints are (a + b) / 2 in f32, a box is (ymin, xmin, ymax, xmax).
+ *   root (keypoint 0)   two one-pixel rectangle outlines in palette[0]: [T(xmin), T(ymin), T(xmax), T(ymax)] and the same
+ *                       box shrunk by 1 on every side.  An outline [x0, y0, x1, y1] is the border of that pixel box; with
+ *                       x1 < x0 or y1 < y0 it draws nothing.
+ *   keypoint k > 0      visbbox: one such outline of its box in palette[k].  Otherwise a disc: with (x, y) the box centre,
+ *                       bx0 = T(x - 2), by0 = T(y - 2), bx1 = T(x + 2), by1 = T(y + 2); the pixel box [bx0, by0, bx1, by1]
+ *                       (4 or 5 pixels each way) without its four corner pixels.
+ *   limb (s, t)         PIL's width-2 line from (x0, y0) to (x1, y1), the truncated box centres of s and t, in palette[s].
+ *                       dx = x1 - x0, dy = y1 - y0; a zero vector draws the pixel (x0, y0).  Otherwise
+ *                       dxmax = RD(dy / hypot(dx, dy)), dymax = RU(dx / hypot(dx, dy)) with
+ *                       RU(f) = floor(f + .5) for f >= 0, -floor(|f| + .5) otherwise, RD(f) = ceil(f - .5) for f >= 0,
+ *                       -ceil(|f| - .5) otherwise (so dxmax = sign(dy) iff 3 dy^2 > dx^2, dymax = sign(dx) iff
+ *                       3 dx^2 > dy^2, else 0), and the quad (x0, y0 + dymax), (x1, y1 + dymax), (x1 + dxmax, y1),
+ *                       (x0 + dxmax, y0) is filled by scan lines over its four edges (vertex i to vertex i + 1):
+ *                       a horizontal edge is drawn as its own clipped horizontal line.  ymin = min(H - 1, the edges'
+ *                       smallest y), ymax = max(0, their largest y), then ymin = max(ymin, 0), ymax = min(ymax, H).  For
+ *                       each row y in [ymin, ymax]: over the non-horizontal edges e (from (ex0, ey0), f32 slope
+ *                       s = (float)(ex1 - ex0) / (float)(ey1 - ey0)) whose y range holds y, collect
+ *                       x = (float)(y - ey0) * s + (float)ex0, twice when y is the edge's largest y and y < ymax; sort;
+ *                       fill [RU(x[i-1]), RD(x[i])] for i = 1, 3, .., a reversed pair swapped, clipped to the frame.
+ *                       The rule is not symmetric in the end points and, rounding being symmetric about zero, not
+ *                       translation-invariant: it is evaluated in frame coordinates.
+ *   grid                after all people, every column x = 0, grid_step, .. < W and every row y = 0, grid_step, .. < H in
+ *                       (110, 110, 110).
+ * A keypoint any of whose four box values is not finite or has |v| >= 2^20 is treated as absent (its limbs too).
+ * Deviations from the reference: PIL raises for an outline with x1 < x0 or y1 < y0 (here: nothing is drawn), paints two
+ * stray pixels below an outline of zero height (here: none), and raises or takes seconds on the out-of-range coordinates;
+ * the mask= paste is not built.
+ *
+ *   src, dst   u8 [batch][height][width][3] RGB device.  dst == src draws in place and stores only drawn pixels; otherwise the
+ *              two must not overlap and every pixel of dst is written (12-byte stores when width % 4 == 0 and both are
+ *              4-byte aligned)
+ *   count      i32 [batch], kp_cell i32 [batch][max_humans][K], bbox f32 [batch][max_humans][K][4]: ppn_decode's outputs
+ *   workspace  ppn_draw_workspace_bytes(cfg, batch, max_humans) bytes, 16-byte aligned: 48 bytes per (person, slot)
+ * Two launches on `stream`, no allocation, no host synchronisation.  Limits (PPN_E_UNSUPPORTED beyond them): batch <= 65535,
+ * height and width <= 32768, max_humans * (K + E) < 2^30.  Any number of primitives may cover one tile.
+ */
+typedef struct ppn_draw_cfg {
+    int32_t K, E;
+    int32_t edge_src[PPN_MAX_EDGES], edge_dst[PPN_MAX_EDGES]; /* limbs in EDGES order */
+    int32_t kp_order[PPN_MAX_KP];                             /* paint order of the keypoints: K entries in [0, K) */
+    uint8_t palette[PPN_MAX_KP][4];                           /* r, g, b, unused */
+    int32_t visbbox, grid, grid_step;                         /* grid_step >= 1 when grid is set */
+} ppn_draw_cfg;
+
+size_t ppn_draw_workspace_bytes(const ppn_draw_cfg* cfg, int32_t batch, int32_t max_humans); /* 0 on a bad argument */
+int ppn_draw_humans(const ppn_draw_cfg* cfg, const uint8_t* src, uint8_t* dst, int32_t batch, int32_t height, int32_t width,
+                    const int32_t* count, const int32_t* kp_cell, const float* bbox, int32_t max_humans, void* workspace,
+                    void* stream);
+
 /* Process-wide tile choice of the large-tile convolution kernel.  0 (default): one launch at a time -- tiles are
  * sized so that the workgroup count fills whole rounds of the 256 CUs.  1: several launches are in flight on
  * different streams (rt.MultiLaneInference) -- a partial last round is filled by the other stream's workgroups, so

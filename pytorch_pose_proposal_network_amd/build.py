@@ -48,6 +48,8 @@ SOURCES = [
     ("ingest.hip", ["-ffp-contract=off"]),
     # augment.hip is bit-exact with a NumPy restatement: no contraction, and the normalisation's f32 divide IEEE-rounded
     ("augment.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
+    # render.hip is bit-exact with PIL's scan-line fill: x = (y - y0) * slope + x0 uncontracted, the slope's divide IEEE-rounded
+    ("render.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
 ]
 
 

@@ -19,6 +19,19 @@ KEYPOINT_NAMES = [
     "thorax", "pelvis", "neck", "top", "stomach",
 ]
 
+# Drawing colours by keypoint name, RGB (config.py:23-42; used by datatest.draw_humans and by render.py)
+COLOR_MAP = {
+    "instance": (143, 35, 35),
+    "left_shoulder": (0, 64, 255), "right_shoulder": (79, 143, 35),
+    "left_elbow": (0, 149, 255), "right_elbow": (106, 255, 0),
+    "left_wrist": (0, 234, 255), "right_wrist": (191, 255, 0),
+    "left_hip": (107, 35, 143), "right_hip": (35, 98, 143),
+    "left_knee": (170, 0, 255), "right_knee": (185, 215, 237),
+    "left_ankle": (220, 185, 237), "right_ankle": (185, 237, 224),
+    "thorax": (255, 255, 0), "pelvis": (255, 0, 170), "neck": (237, 185, 185), "top": (255, 0, 0),
+    "stomach": (79, 35, 35),
+}
+
 EDGES_BY_NAME = [
     ("instance", "neck"), ("neck", "thorax"),
     ("thorax", "left_shoulder"), ("left_shoulder", "left_elbow"), ("left_elbow", "left_wrist"),
@@ -97,3 +110,10 @@ def tree_tables():
                 order.append(e)
     assert sorted(order) == list(range(E))
     return src, dst, order
+
+
+def kp_paint_order():
+    """The order in which datatest.get_humans_by_feature inserts keypoints into a person's dict (datatest.py:104-125),
+    hence the order draw_humans paints them in: the root, then each tree edge's target, parent before child."""
+    _, dst, order = tree_tables()
+    return [ROOT_NODE] + [dst[e] for e in order]

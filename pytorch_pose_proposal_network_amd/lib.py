@@ -107,6 +107,14 @@ class WgradDesc(C.Structure):
         ("workspace_bytes", C.c_uint64)]
 
 
+class DrawCfg(C.Structure):
+    """ppn_draw_cfg (csrc/render.hip)."""
+    _fields_ = [("K", C.c_int32), ("E", C.c_int32), ("edge_src", C.c_int32 * PPN_MAX_EDGES),
+                ("edge_dst", C.c_int32 * PPN_MAX_EDGES), ("kp_order", C.c_int32 * PPN_MAX_KP),
+                ("palette", (C.c_uint8 * 4) * PPN_MAX_KP), ("visbbox", C.c_int32), ("grid", C.c_int32),
+                ("grid_step", C.c_int32)]
+
+
 class PPNError(RuntimeError):
     pass
 
@@ -241,6 +249,9 @@ _SIGNATURES.update({
                                     C.c_int32, C.c_int32, C.c_void_p]),
     "ppn_augment_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 3),
     "ppn_augment_people": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p] * 4),
+    "ppn_draw_workspace_bytes": (C.c_size_t, [C.POINTER(DrawCfg), C.c_int32, C.c_int32]),
+    "ppn_draw_humans": (C.c_int, [C.POINTER(DrawCfg), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
 })
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1,0 +1,168 @@
+"""Drawing the decoded people on the device (reference: datatest.py:162-232, `draw_humans`) over csrc/render.hip.
+
+* ``draw_people(frames_u8, result)``     -- the device path: u8 RGB frames [B,H,W,3] + the DecodeResult as it lives on the
+                                            device -> drawn frames, on the current stream, no host synchronisation.
+* ``Renderer(batch, max_humans)``        -- owns the workspace for a fixed geometry so repeated calls allocate nothing.
+* ``draw_humans(keypoint_names, edges, pil_image, humans, ...)`` -- same name / arguments / return as datatest.py:162.
+
+The pixels are the ones PIL's ImageDraw paints for the reference's calls (rules and deviations: include/ppn.h,
+ppn_draw_humans; NumPy restatement tests/render_ref.py).  The reference's ``mask=`` paste is not built.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import config as cfg
+from . import decode as D
+from . import lib as L
+
+
+def default_palette(keypoint_names: Sequence[str] = cfg.KEYPOINT_NAMES):
+    return [cfg.COLOR_MAP[n] for n in keypoint_names]
+
+
+def make_cfg(visbbox: bool = False, grid: bool = False, grid_step: int = 16, palette=None, kp_order=None,
+             edges=None, num_keypoints: Optional[int] = None) -> L.DrawCfg:
+    """ppn_draw_cfg for the skeleton of config.py (or `edges` / `num_keypoints` / `kp_order` of another one)."""
+    edges = cfg.EDGES if edges is None else [tuple(e) for e in edges]
+    K = cfg.K if num_keypoints is None else int(num_keypoints)
+    palette = default_palette() if palette is None else palette
+    kp_order = (cfg.kp_paint_order() if K == cfg.K else list(range(K))) if kp_order is None else list(kp_order)
+    if not 1 <= K <= L.PPN_MAX_KP or len(edges) > L.PPN_MAX_EDGES:
+        raise ValueError(f"{K} keypoints / {len(edges)} edges: at most {L.PPN_MAX_KP} / {L.PPN_MAX_EDGES}")
+    if len(palette) != K or any(len(c) != 3 or min(c) < 0 or max(c) > 255 for c in palette):
+        raise ValueError(f"palette must hold {K} (r, g, b) triples in 0..255")
+    if len(kp_order) != K or any(not 0 <= int(k) < K for k in kp_order):
+        raise ValueError(f"kp_order must hold {K} keypoint indices")
+    if any(not (0 <= int(s) < K and 0 <= int(t) < K) for s, t in edges):
+        raise ValueError("edges must join keypoint indices")
+    if grid and int(grid_step) < 1:
+        raise ValueError(f"grid_step {grid_step} < 1")
+    c = L.DrawCfg()
+    c.K, c.E = K, len(edges)
+    for i, (s, t) in enumerate(edges):
+        c.edge_src[i], c.edge_dst[i] = int(s), int(t)
+    for i in range(K):
+        c.kp_order[i] = int(kp_order[i])
+        for j in range(3):
+            c.palette[i][j] = int(palette[i][j])
+    c.visbbox, c.grid, c.grid_step = int(bool(visbbox)), int(bool(grid)), int(grid_step) if grid else 1
+    return c
+
+
+def _check_frames(frames_u8, out):
+    if not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8:
+        raise ValueError("frames must be a uint8 tensor [B,H,W,3]")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
+        raise ValueError(f"frames must be a contiguous [B,H,W,3] tensor, got {tuple(frames_u8.shape)}")
+    if not frames_u8.is_cuda:
+        raise ValueError("frames must live on the device")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != frames_u8.shape
+                            or not out.is_contiguous() or out.device != frames_u8.device):
+        raise ValueError("out must be a contiguous uint8 tensor of the frames' shape on their device")
+
+
+class Renderer:
+    """Owns the rasteriser's workspace (48 bytes per person and slot) for a fixed (batch, max_humans); a call only
+    enqueues two launches on the current stream."""
+
+    def __init__(self, batch: int, max_humans: int, device="cuda"):
+        self.lib = L.load()
+        self.batch, self.max_humans = int(batch), int(max_humans)
+        ws = self.lib.ppn_draw_workspace_bytes(C.byref(make_cfg()), self.batch, self.max_humans)
+        if ws == 0:
+            raise ValueError(f"bad renderer geometry: batch {batch}, max_humans {max_humans}")
+        self.workspace = torch.empty(ws // 4, dtype=torch.int32, device=torch.device(device))
+
+    def __call__(self, frames_u8: torch.Tensor, result: D.DecodeResult, visbbox: bool = False, gridOn: bool = False,
+                 out: Optional[torch.Tensor] = None, palette=None, outsize=None) -> torch.Tensor:
+        """Draw `result`'s people onto `frames_u8` (u8 RGB [B,H,W,3] on the device).  out=None: a new tensor; out=frames_u8:
+        in place; any other `out` is overwritten entirely.  gridOn adds the reference's cell grid with step
+        int(W / outW), `outsize` = (outW, outH) defaulting to config.OUTSIZE.  Returns the drawn tensor."""
+        _check_frames(frames_u8, out)
+        B, H, W, _ = frames_u8.shape
+        m = result.max_humans
+        if B != self.batch or m != self.max_humans:
+            raise ValueError(f"renderer built for batch {self.batch} x {self.max_humans} people, got {B} x {m}")
+        if tuple(result.count.shape) != (B,) or tuple(result.kp_cell.shape) != (B, m, cfg.K) or \
+                tuple(result.bbox.shape) != (B, m, cfg.K, 4):
+            raise ValueError("result does not hold count [B], kp_cell [B,M,K] and bbox [B,M,K,4]")
+        step = int(W / (outsize if outsize is not None else cfg.OUTSIZE)[0]) if gridOn else 1
+        c = make_cfg(visbbox, gridOn, step, palette)
+        if out is None:
+            out = torch.empty_like(frames_u8)
+        elif out.data_ptr() != frames_u8.data_ptr():
+            lo, hi = sorted((out.data_ptr(), frames_u8.data_ptr()))
+            if lo + frames_u8.numel() > hi:
+                raise ValueError("out must be the frames themselves or not overlap them")
+        L.check(self.lib.ppn_draw_humans(C.byref(c), frames_u8.data_ptr(), out.data_ptr(), B, H, W,
+                                         result.count.data_ptr(), result.kp_cell.data_ptr(), result.bbox.data_ptr(), m,
+                                         self.workspace.data_ptr(), L.current_stream_ptr()), "ppn_draw_humans")
+        return out
+
+
+def draw_people(frames_u8: torch.Tensor, result: D.DecodeResult, visbbox: bool = False, gridOn: bool = False,
+                out: Optional[torch.Tensor] = None, palette=None, outsize=None) -> torch.Tensor:
+    """One-off Renderer call (allocates the workspace; keep a Renderer for repeated use).  Runs on the current stream
+    without a host synchronisation."""
+    _check_frames(frames_u8, out)
+    return Renderer(frames_u8.shape[0], result.max_humans, frames_u8.device)(frames_u8, result, visbbox, gridOn, out,
+                                                                            palette, outsize)
+
+
+def pack_humans(humans, num_keypoints: int = cfg.K):
+    """The reference's list of {keypoint: [ymin, xmin, ymax, xmax]} dicts -> (count i32[1], kp_cell i32[1,M,K],
+    bbox f32[1,M,K,4]) NumPy arrays, M = max(len(humans), 1)."""
+    n, K = len(humans), num_keypoints
+    count = np.array([n], np.int32)
+    kp_cell = np.full((1, max(n, 1), K), -1, np.int32)
+    bbox = np.zeros((1, max(n, 1), K, 4), np.float32)
+    for i, hm in enumerate(humans):
+        for k, b in hm.items():
+            if not 0 <= int(k) < K:
+                raise ValueError(f"person {i}: keypoint {k} is not in 0..{K - 1}")
+            kp_cell[0, i, int(k)] = 0
+            bbox[0, i, int(k)] = np.asarray(b, np.float32)
+    return count, kp_cell, bbox
+
+
+def draw_humans(keypoint_names, edges, pil_image, humans, mask=None, visbbox=False, gridOn=False):
+    """Drop-in for datatest.py:162-232: draws `humans` onto `pil_image` (a PIL image, updated and returned as the reference
+    does; or a u8 HxWx3 array, then a new array is returned) with the HIP rasteriser -- the dicts are packed, one frame
+    goes to the device and comes back.
+
+    Keypoints are always painted in config.kp_paint_order(), the order get_humans_by_feature builds its dicts in, not in
+    the dicts' own order; the grid step is int(width / decode.outsize[0]).  `mask` is not built."""
+    if mask is not None:
+        raise NotImplementedError("draw_humans: the mask= paste of the reference is not built")
+    K = len(keypoint_names)
+    c = make_cfg(visbbox, gridOn, 1, default_palette(keypoint_names), None, edges, K)   # validates before any device work
+    is_array = isinstance(pil_image, np.ndarray)
+    img = np.array(pil_image if is_array else pil_image.convert("RGB"), order="C")     # a writable copy
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("draw_humans expects an RGB image (u8 HxWx3)")
+    H, W, _ = img.shape
+    if gridOn:
+        c.grid_step = int(W / D.outsize[0])
+        if c.grid_step < 1:
+            raise ValueError(f"image width {W} is below the grid's {D.outsize[0]} cells")
+    count, kp_cell, bbox = pack_humans(humans, K)
+    lib = L.load()
+    dev = torch.device("cuda")
+    frame = torch.from_numpy(img).unsqueeze(0).to(dev)
+    ws = torch.empty(max(lib.ppn_draw_workspace_bytes(C.byref(c), 1, kp_cell.shape[1]), 16) // 4, dtype=torch.int32,
+                     device=dev)
+    cd, kd, bd = (torch.from_numpy(a).to(dev) for a in (count, kp_cell, bbox))
+    L.check(lib.ppn_draw_humans(C.byref(c), frame.data_ptr(), frame.data_ptr(), 1, H, W, cd.data_ptr(), kd.data_ptr(),
+                                bd.data_ptr(), kp_cell.shape[1], ws.data_ptr(), L.current_stream_ptr()),
+            "ppn_draw_humans")
+    drawn = frame[0].cpu().numpy()
+    if is_array:
+        return drawn
+    from PIL import Image
+    pil_image.paste(Image.fromarray(drawn).convert(pil_image.mode))
+    return pil_image

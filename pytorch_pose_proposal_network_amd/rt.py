@@ -6,9 +6,11 @@
 ``inference`` keeps the reference's argument list; what it does differently is *where* things run: the
 uint8 frame is uploaded once (442 KB), normalisation + the whole conv stack + head run as HIP kernels, the
 head tensor never leaves the device (the reference copies all 17.5 MB of it to the host in seven slices,
-rt_test.py:109-120) and only the compact people list (<= 80 KB) comes back.  Webcam capture, matplotlib
-animation and drawing (rt_test.py:150-205, datatest.py:162-232) are out of scope: ``inference`` returns the
-reference's ``(humans, scores)`` instead of a PIL image; pass ``draw=callable`` to post-process on the host.
+rt_test.py:109-120) and only the compact people list (<= 80 KB) comes back.  Webcam capture and the matplotlib
+animation (rt_test.py:150-205) are out of scope.  ``inference`` returns the reference's ``(humans, scores)`` instead of a
+PIL image (pass ``draw=callable`` to post-process on the host); ``inference_drawn`` returns the drawn image as
+rt_test.inference does and ``inference_batch_drawn`` the drawn batch, both painted on the device (render.py,
+datatest.py:162-232).
 """
 from __future__ import annotations
 
@@ -112,6 +114,48 @@ def inference_batch(frames_u8: torch.Tensor, model: PoseProposalNet, decoder: Op
         decoder = D.Decoder(b, (h, w), (frames_u8.shape[1], frames_u8.shape[2]), model.local_grid_size,
                             detection_thresh, device=unary.device)
     return decoder.decode_fused(unary, keys)
+
+
+def inference_drawn(image, model: PoseProposalNet, outsize, local_grid_size, detection_thresh: float = 0.15,
+                    visbbox: bool = False, gridOn: bool = False):
+    """rt_test.py:87-147 including its last step (rt_test.py:135-147): the frame with the detected people drawn on it by
+    the HIP rasteriser (render.py), as a PIL image -- a u8 [H,W,3] array where PIL is absent.  The people lists never
+    leave the device; one frame goes up and one comes back."""
+    from . import render as R
+    model.eval()
+    if isinstance(image, torch.Tensor) and image.is_cuda:
+        frames = image if image.dim() == 4 else image.unsqueeze(0)
+        if frames.dtype != torch.uint8 or frames.shape[0] != 1 or frames.shape[3] != 3:
+            raise ValueError("inference_drawn expects a uint8 [1,H,W,3] / [H,W,3] RGB frame")
+        frames = frames.contiguous()
+    else:
+        img = np.asarray(image)
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("inference_drawn expects a uint8 HxWx3 RGB frame")
+        frames = torch.from_numpy(np.ascontiguousarray(img)).unsqueeze(0).cuda(non_blocking=True)
+    head = model.forward_u8(frames)
+    res = D.decode_heads(head, insize_hw=(frames.shape[1], frames.shape[2]), local_grid=local_grid_size,
+                         detection_thresh=detection_thresh)
+    drawn = R.draw_people(frames, res, visbbox=visbbox, gridOn=gridOn, outsize=outsize)[0].cpu().numpy()
+    try:
+        from PIL import Image
+    except ImportError:
+        return drawn
+    return Image.fromarray(drawn)
+
+
+def inference_batch_drawn(frames_u8: torch.Tensor, model: PoseProposalNet, decoder: Optional[D.Decoder] = None,
+                          renderer=None, out: Optional[torch.Tensor] = None, detection_thresh: float = 0.15,
+                          visbbox: bool = False, gridOn: bool = False):
+    """inference_batch plus the drawing, all on the device: u8 [B,S,S,3] CUDA frames -> (DecodeResult, drawn u8 frames).
+    `out` as in render.Renderer (None: a new tensor, `frames_u8` itself: in place); pass a Decoder and a render.Renderer to
+    allocate nothing per call."""
+    from . import render as R
+    res = inference_batch(frames_u8, model, decoder, detection_thresh)
+    if renderer is None:
+        renderer = R.Renderer(frames_u8.shape[0], res.max_humans, frames_u8.device)
+    outW = frames_u8.shape[2] // 16
+    return res, renderer(frames_u8, res, visbbox=visbbox, gridOn=gridOn, out=out, outsize=(outW, frames_u8.shape[1] // 16))
 
 
 class InferencePipeline:
