@@ -517,6 +517,53 @@ int ppn_draw_humans(const ppn_draw_cfg* cfg, const uint8_t* src, uint8_t* dst, i
                     const int32_t* count, const int32_t* kp_cell, const float* bbox, int32_t max_humans, void* workspace,
                     void* stream);
 
+/*
+ * The per-image matching of a validation epoch on the device (main.py:1017-1172 validate / 886-1014 test_output ->
+ * datatest.evaluation -> eval_helpers.assignGTmulti, eval_helpers.py:300-468), csrc/validate.hip: one batch of compact
+ * people lists against the resident ground truth of the whole validation set, one workgroup per image, emitting the
+ * per-person, per-joint (score, label) records evaluate.assign_gt_multi produces (tests/validate_ref.py restates the rules
+ * below in NumPy; tests/golden/eval_cases.npz pins them to the reference).  K = 18: keypoint 0 is the instance, keypoint
+ * j + 1 is joint j of the PPN_MATCH_JOINTS = 17.
+ *
+ * For batch image b with n = image_index[b], P = min(max(count[b], 0), max_humans), G = gt_count[n]:
+ *   predicted joint j   of person p is present iff kp_cell[b][p][j + 1] >= 0; its point is x = (box[1] + box[3]) / 2,
+ *                       y = (box[0] + box[2]) / 2 of its box (ymin, xmin, ymax, xmax), its score score[b][p][j + 1].  A missing
+ *                       joint is the point (0, 0) with score 0 and takes part in the matching like any other.
+ *   match[p][g][j]      sqrt(dx * dx + dy * dy) / gt_head[n][g] <= dist_thresh with dx = gt_x - x, dy = gt_y - y: every step
+ *                       an f32 operation rounded on its own (no contraction, IEEE square root and division, no reciprocal),
+ *                       the comparison in f32.  A NaN or infinite quotient (head size 0) is no match.
+ *   cnt[p][g]           the number of matching joints; comparisons are on these integers.
+ *   best_gt[p]          the first g with the largest cnt[p][.].
+ *   claim               ground-truth person g is claimed by the first p, in ascending p, with the largest cnt[p][g] among the
+ *                       p whose best_gt is g; a largest value of 0 claims nobody.
+ *   rec_label[n][p][j]  match[p][g][j] for the one g that p claimed, otherwise 0;  rec_score[n][p][j] the joint's score.
+ *   rec_count[n]        P when G > 0, otherwise 0: a frame without ground truth is dropped with its predictions (cleanupData).
+ * Rows p < rec_count[n] of rec_score / rec_label are written and no others; rec_count[n] is written whenever n is valid.
+ * image_index[b] == -1 marks a padding image of a ragged last batch: nothing is written for it.  The valid indices of one
+ * call must differ from each other.  Errors found on the device OR a bit into *flags (which the caller zeroes once per epoch)
+ * and write nothing for that image: PPN_MATCH_FLAG_INDEX for an index outside [-1, n_images), PPN_MATCH_FLAG_GT_COUNT for a
+ * gt_count outside [0, gmax].
+ *
+ *   count       i32 [batch], kp_cell i32 [batch][max_humans][18], bbox f32 [batch][max_humans][18][4] (16-byte aligned),
+ *               score f32 [batch][max_humans][18]: ppn_decode's outputs as they live on the device
+ *   gt_xy       f32 [n_images][gmax][17][2] (x, y; 8-byte aligned), gt_head f32 [n_images][gmax], gt_count i32 [n_images]
+ *   rec_score   f32 [n_images][max_humans][17], rec_label u8 [n_images][max_humans][17], rec_count i32 [n_images]: buffers
+ *               of a whole epoch, rows addressed by image_index, so that an epoch needs one D2H at its end
+ * One launch on `stream`, no allocation, no host synchronisation, no D2H: the call can be captured into a graph.  Integer
+ * maxima only, no floating-point atomics: two runs give identical bytes.  Limits (PPN_E_UNSUPPORTED beyond them):
+ * gmax <= PPN_MATCH_MAX_GT, max_humans <= PPN_MATCH_MAX_PEOPLE.
+ */
+#define PPN_MATCH_JOINTS 17
+#define PPN_MATCH_MAX_GT 64
+#define PPN_MATCH_MAX_PEOPLE 1024
+#define PPN_MATCH_FLAG_INDEX 1
+#define PPN_MATCH_FLAG_GT_COUNT 2
+
+int ppn_pckh_match(const int32_t* count, const int32_t* kp_cell, const float* bbox, const float* score, int32_t batch,
+                   int32_t max_humans, const float* gt_xy, const float* gt_head, const int32_t* gt_count, int32_t n_images,
+                   int32_t gmax, const int32_t* image_index, float dist_thresh, float* rec_score, uint8_t* rec_label,
+                   int32_t* rec_count, int32_t* flags, void* stream);
+
 /* Process-wide tile choice of the large-tile convolution kernel.  0 (default): one launch at a time -- tiles are
  * sized so that the workgroup count fills whole rounds of the 256 CUs.  1: several launches are in flight on
  * different streams (rt.MultiLaneInference) -- a partial last round is filled by the other stream's workgroups, so

@@ -50,6 +50,8 @@ SOURCES = [
     ("augment.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
     # render.hip is bit-exact with PIL's scan-line fill: x = (y - y0) * slope + x0 uncontracted, the slope's divide IEEE-rounded
     ("render.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
+    # validate.hip is bit-exact with NumPy's f32 distance at the PCKh threshold: dx*dx + dy*dy uncontracted, IEEE sqrt and divide
+    ("validate.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
 ]
 
 

@@ -15,6 +15,9 @@ decode.DecodeResult.to_humans() returns.  Quirks reproduced on purpose: every pr
 predictions (cleanupData, eval_helpers.py:202-218); the head size is 0.6 x the diagonal of the instance box whose
 corners use floor division (datatest.py:331-334, eval_helpers.py:82-84); the f32 arithmetic of the reference's NumPy
 scalars is kept so that distances exactly at the 0.5 threshold fall on the same side.
+
+The per-image matching in front of the AP curve also runs on the device, once per batch and without a read-back
+(validate.py over ppn_pckh_match); `metrics_from_records` turns its packed records into the same 8 numbers.
 """
 from __future__ import annotations
 
@@ -142,6 +145,27 @@ def evaluation(list_: Sequence) -> List[float]:
         gxy = np.asarray(gt_kps, np.float32).reshape(len(gt_bboxes), N_JOINTS, 2)
         frames.append((pxy, psc, gxy, _head_sizes(gt_bboxes)))
     return get_cum(compute_metrics(*assign_gt_multi(frames)))
+
+
+def metrics_from_records(rec_score, rec_label, rec_count, gt_count) -> List[float]:
+    """The 8 AP values from the packed records of a validation epoch (validate.match_people / ppn_pckh_match):
+    rec_score f32[N,M,17], rec_label u8[N,M,17], rec_count i32[N] (people recorded per image), gt_count i32[N].  Images
+    without ground truth are dropped (cleanupData); the rest are flattened image-major, then in person order -- the order
+    `evaluation` concatenates them in, which decides how _compute_rpc's argsort breaks the ties among the many score-0
+    records of missing joints."""
+    rec_score, rec_label = np.asarray(rec_score, np.float32), np.asarray(rec_label)
+    rec_count, gt_count = np.asarray(rec_count).astype(np.int64), np.asarray(gt_count).astype(np.int64)
+    if rec_score.ndim != 3 or rec_score.shape[2] != N_JOINTS or rec_label.shape != rec_score.shape:
+        raise ValueError(f"records must be [N, M, {N_JOINTS}] arrays of one shape")
+    if rec_count.shape != (len(rec_score),) or gt_count.shape != rec_count.shape:
+        raise ValueError("rec_count and gt_count must hold one entry per image")
+    if rec_count.size and (rec_count.min() < 0 or rec_count.max() > rec_score.shape[1]):
+        raise ValueError("rec_count beyond the records' person slots")
+    kept = np.flatnonzero(gt_count > 0)
+    scores_all = [[rec_score[n, :rec_count[n], j] for n in kept] for j in range(N_JOINTS)]
+    labels_all = [[rec_label[n, :rec_count[n], j].astype(np.int8) for n in kept] for j in range(N_JOINTS)]
+    n_gt = np.repeat(gt_count[kept][None, :].astype(np.float64), N_JOINTS, axis=0)
+    return get_cum(compute_metrics(scores_all, labels_all, n_gt))
 
 
 def people_as_ground_truth(res: dict):

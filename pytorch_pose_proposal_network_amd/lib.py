@@ -14,7 +14,9 @@ PPN_F32, PPN_BF16, PPN_F16, PPN_F16X3 = 0, 1, 2, 3
 PPN_CONV_NO_FILTER_BANK, PPN_CONV_SHARED_GPU, PPN_CONV_OUT_BF16, PPN_CONV_X3_PLAIN_OUT = 1, 2, 4, 8   # ppn_conv_desc.flags
 PPN_CONV_SPLIT_K = 16               # split-K pair of launches (csrc/conv_splitk.hip); needs ConvDesc.splitk_ws
 PPN_ACT_NONE, PPN_ACT_RELU, PPN_ACT_LRELU, PPN_ACT_SIGMOID = 0, 1, 2, 3
-PPN_STEM_RAW_S2 = 1 << 16           # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
+PPN_MATCH_JOINTS, PPN_MATCH_MAX_GT, PPN_MATCH_MAX_PEOPLE = 17, 64, 1024     # ppn_pckh_match (csrc/validate.hip)
+PPN_MATCH_FLAG_INDEX, PPN_MATCH_FLAG_GT_COUNT = 1, 2
+PPN_STEM_RAW_S2 = 1 << 16          # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
 
 
 def PPN_STEM_IO(internal: int, out: int) -> int:
@@ -252,6 +254,8 @@ _SIGNATURES.update({
     "ppn_draw_workspace_bytes": (C.c_size_t, [C.POINTER(DrawCfg), C.c_int32, C.c_int32]),
     "ppn_draw_humans": (C.c_int, [C.POINTER(DrawCfg), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ppn_pckh_match": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_float] + [C.c_void_p] * 5),
 })
 
 EXPORTS = tuple(_SIGNATURES)

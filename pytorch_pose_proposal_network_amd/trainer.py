@@ -370,9 +370,8 @@ class PPNTrainer:
         restore(ckpt["optimizerR"], [(self.task.exp_avg, self.task.exp_avg_sq)], set_r)
         return int(ckpt.get("epoch", 0))
 
-    def get_baseloss(self, batches):
-        """main.py:578-621: the five losses in EVAL mode (running BN statistics) averaged over `batches`, an iterable
-        of (x f32[B,3,H,W], targets dict); sets and returns self.base (f32[5] on the device)."""
+    def _eval_net(self):
+        """The eval-mode network (running BN statistics folded) of the current parameters: model.eval() of main.py:586, 1030."""
         from . import drn, model
         net = model.PoseProposalNet(getattr(drn, self.arch)(), insize=self.insize,
                                     outsize=(self.insize[0] // 16, self.insize[1] // 16),
@@ -380,6 +379,12 @@ class PPNTrainer:
         net = net.cuda(self.device)
         net.load_state_dict(self.state_dict())
         net.eval()
+        return net
+
+    def get_baseloss(self, batches):
+        """main.py:578-621: the five losses in EVAL mode (running BN statistics) averaged over `batches`, an iterable
+        of (x f32[B,3,H,W], targets dict); sets and returns self.base (f32[5] on the device)."""
+        net = self._eval_net()
         total = torch.zeros(5, dtype=torch.float32, device=self.device)
         n = 0
         for x, targets in batches:
@@ -390,6 +395,22 @@ class PPNTrainer:
             raise ValueError("get_baseloss needs at least one batch")
         self.base = total / n
         return self.base
+
+    def validate(self, batches, gt, max_humans: int = 64, detection_thresh: float = 0.15):
+        """main.py:1017-1172: one validation epoch in EVAL mode over `batches`, an iterable of (x f32[b,3,H,W], image_index
+        i32[b] -- rows of `gt`, a validate.GroundTruth -- and the targets dict or None); the first batch sets the batch
+        size, a later one may be shorter.  Returns (losses.avg with the current task weights, the 8 AP values); nothing is
+        read back before the end (validate.Validator)."""
+        from .validate import Validator
+        net, v = self._eval_net(), None
+        for x, image_index, targets in batches:
+            if v is None:
+                v = Validator(net, gt, x.shape[0], self.criterion, self.task.w, detection_thresh, max_humans)
+                v.reset()
+            v.step(x, image_index, targets)
+        if v is None:
+            raise ValueError("validate needs at least one batch")
+        return v.finish()
 
     def adjust_learning_rate(self, epoch: int):
         """main.py:1222-1231, called on optimizerM once per epoch (main.py:406): halve the rate every 300 epochs."""
