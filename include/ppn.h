@@ -564,6 +564,54 @@ int ppn_pckh_match(const int32_t* count, const int32_t* kp_cell, const float* bb
                    int32_t gmax, const int32_t* image_index, float dist_thresh, float* rec_score, uint8_t* rec_label,
                    int32_t* rec_count, int32_t* flags, void* stream);
 
+/*
+ * Horizontal-flip test-time averaging (no counterpart in the reference), csrc/tta.hip: the network sees a frame and its
+ * left-right mirror image, the second head is mapped back and averaged with the first, and only then the decode runs.
+ * Geometry as in ppn_decode_cfg; the heads are f32 [batch, C, H, W] NCHW with C = 6K + E*sH*sW: six unary groups resp, conf,
+ * x, y, w, h of K channels each, then e[E][sH][sW] (limb channel e_chan(e, ly, lx) = 6K + (e*sH + ly)*sW + lx).
+ *   kp_mirror[k]     the keypoint whose name has left_ / right_ swapped, k itself where there is no such prefix;
+ *   edge_mirror[e]   the edge (kp_mirror[src], kp_mirror[dst]).  Both must be involutions of [0, K) / [0, E).
+ * With A the head of the frame and Bm the head of the mirrored frame, mirror(Bm) is, per image, at cell (i, j):
+ *   groups resp, conf, y, w, h    Bm[g, kp_mirror[k], i, W-1-j]
+ *   group x                       1.0f - Bm[x, kp_mirror[k], i, W-1-j]
+ *   limbs                         Bm[e_chan(edge_mirror[e], ly, sW-1-lx), i, W-1-j]
+ * and the merged head is M = (A + mirror(Bm)) * 0.5f elementwise in f32: one IEEE addition, then one multiplication, no
+ * contraction, no reassociation, subnormals kept -- NumPy's ((a + m) * np.float32(0.5)) bit for bit (tests/tta_ref.py).
+ * Precondition: inputs in [0, 1] (sigmoid outputs); the result for NaNs or negative values is unspecified.
+ */
+typedef struct ppn_tta_cfg {
+    int32_t K, E, sH, sW, H, W;            /* as in ppn_decode_cfg */
+    int32_t kp_mirror[PPN_MAX_KP];
+    int32_t edge_mirror[PPN_MAX_EDGES];
+} ppn_tta_cfg;
+
+/*
+ * Reads head_a (A) and head_b (Bm) once and writes what ppn_decode_fused takes:
+ *   out_unary  f32 [batch, 6K, H, W]   the first 6K channels of M
+ *   out_keys   u64 [batch, E, H, W]    (uint64)float_bits(max_s M[e, s, cell]) << 32 | ~(uint32)s_first, with s = ly*sW + lx
+ *                                      in MERGED order and s_first the lowest s attaining the maximum (the key format of
+ *                                      ppn_conv_desc.argmax_keys)
+ *   out_head   f32 [batch, C, H, W] or NULL: M in full, written only when given; must not overlap head_a / head_b
+ * One unary launch and one limb launch on `stream`; no allocation, no host synchronisation, no memset node.  When the
+ * window is split across workgroups the unary launch clears out_keys and the slices are combined by a u64 atomic maximum:
+ * the largest value, then the lowest s, in any order, so two runs give identical bytes.  The environment knob PPN_TTA_SPLIT = n, read at
+ * every call, sets the number of window slices per (edge, image) (default: chosen from batch so that the grid fills the GPU);
+ * results do not depend on it.  PPN_E_INVALID before anything is launched for: a NULL cfg / head_a / head_b / out_unary /
+ * out_keys, K outside 1..PPN_MAX_KP, E outside 0..PPN_MAX_EDGES, a non-positive window, grid or batch, a mirror table that
+ * indexes out of range or is not an involution, an output overlapping an input, a misaligned pointer.
+ */
+int ppn_tta_merge(const ppn_tta_cfg* cfg, const float* head_a, const float* head_b, int32_t batch, float* out_unary,
+                  uint64_t* out_keys, float* out_head, void* stream);
+
+/*
+ * The doubled batch of a flip-averaged forward: dst holds 2 * rows rows of `width` elements of elem_bytes bytes; its first
+ * `rows` rows are a copy of src, row rows + r is row r of src with its elements in reverse order.
+ *   elem_bytes 3   u8 [B,H,W,3] RGB frames: rows = B*H, width = W     (dst = a plan's u8 input buffer of batch 2B)
+ *   elem_bytes 4   f32 [B,3,H,W] inputs:    rows = B*3*H, width = W   (4-byte aligned)
+ * dst must not overlap src.  One launch on `stream`; rows = 0 is a no-op.
+ */
+int ppn_tta_stage(const void* src, void* dst, int64_t rows, int32_t width, int32_t elem_bytes, void* stream);
+
 /* Process-wide tile choice of the large-tile convolution kernel.  0 (default): one launch at a time -- tiles are
  * sized so that the workgroup count fills whole rounds of the 256 CUs.  1: several launches are in flight on
  * different streams (rt.MultiLaneInference) -- a partial last round is filled by the other stream's workgroups, so

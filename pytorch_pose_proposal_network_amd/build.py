@@ -52,6 +52,8 @@ SOURCES = [
     ("render.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
     # validate.hip is bit-exact with NumPy's f32 distance at the PCKh threshold: dx*dx + dy*dy uncontracted, IEEE sqrt and divide
     ("validate.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
+    # tta.hip is bit-exact with NumPy's (a + b) * 0.5 in f32: the add and the multiply stay two IEEE operations
+    ("tta.hip", ["-ffp-contract=off"]),
 ]
 
 

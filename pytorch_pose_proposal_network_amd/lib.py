@@ -117,6 +117,12 @@ class DrawCfg(C.Structure):
                 ("grid_step", C.c_int32)]
 
 
+class TtaCfg(C.Structure):
+    """ppn_tta_cfg (csrc/tta.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("K", "E", "sH", "sW", "H", "W")] + [
+        ("kp_mirror", C.c_int32 * PPN_MAX_KP), ("edge_mirror", C.c_int32 * PPN_MAX_EDGES)]
+
+
 class PPNError(RuntimeError):
     pass
 
@@ -256,6 +262,8 @@ _SIGNATURES.update({
                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ppn_pckh_match": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_float] + [C.c_void_p] * 5),
+    "ppn_tta_merge": (C.c_int, [C.POINTER(TtaCfg), C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4),
+    "ppn_tta_stage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
 })
 
 EXPORTS = tuple(_SIGNATURES)

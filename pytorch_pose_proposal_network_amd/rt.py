@@ -77,12 +77,29 @@ def grab_frame(cap, size: int = 384, out: Optional[torch.Tensor] = None):
     return ret, ingest_frames(torch.from_numpy(f).unsqueeze(0).cuda(non_blocking=True), size, out)
 
 
+def _decode_flip_averaged(frames: torch.Tensor, model: PoseProposalNet, decoder: Optional[D.Decoder],
+                          detection_thresh: float, merger=None) -> D.DecodeResult:
+    """Horizontal-flip test-time averaging (tta.py): [frames | frames mirrored] staged straight into the plan's input of
+    batch 2B, one forward with a materialised head pair, ppn_tta_merge, Decoder.decode_fused."""
+    from .tta import FlipMerger
+    frames = frames.contiguous()
+    b, h, w, _ = frames.shape
+    if merger is None:
+        merger = FlipMerger(b, (h // 16, w // 16), model.local_grid_size, frames.device)
+    pair = merger.stage(frames, out=model.input_buffer(2 * b, h, w))
+    unary, keys = merger.merge(model.forward_u8(pair, fused_decode=False))
+    if decoder is None:
+        decoder = D.Decoder(b, (h // 16, w // 16), (h, w), model.local_grid_size, detection_thresh, device=frames.device)
+    return decoder.decode_fused(unary, keys)
+
+
 def inference(image, model: PoseProposalNet, outsize, local_grid_size, detection_thresh: float = 0.15,
-              draw: Optional[Callable] = None):
+              draw: Optional[Callable] = None, flip_tta: bool = False):
     """rt_test.py:87-147 for one RGB frame (u8 [S,S,3] array / PIL image / tensor).
 
     Returns ``(humans, scores)`` exactly as datatest.get_humans_by_feature does (lists of dicts
-    keypoint -> [ymin,xmin,ymax,xmax] / keypoint -> delta), or ``draw(image, humans, scores)`` if given."""
+    keypoint -> [ymin,xmin,ymax,xmax] / keypoint -> delta), or ``draw(image, humans, scores)`` if given.
+    ``flip_tta=True``: the people of the head averaged with the mirrored frame's head (tta.py)."""
     model.eval()
     if isinstance(image, torch.Tensor) and image.is_cuda:             # what grab_frame() returns: already on the device
         frames = image if image.dim() == 4 else image.unsqueeze(0)
@@ -95,10 +112,13 @@ def inference(image, model: PoseProposalNet, outsize, local_grid_size, detection
             raise ValueError("inference expects a uint8 HxWx3 RGB frame")
         frames = torch.from_numpy(np.ascontiguousarray(img)).unsqueeze(0).cuda(non_blocking=True)
         hw = (img.shape[0], img.shape[1])
-    head = model.forward_u8(frames)
     outW, outH = outsize
-    res = D.decode_heads(head, insize_hw=hw, local_grid=local_grid_size,
-                         detection_thresh=detection_thresh)
+    if flip_tta:
+        res = _decode_flip_averaged(frames, model, None, detection_thresh)
+    else:
+        head = model.forward_u8(frames)
+        res = D.decode_heads(head, insize_hw=hw, local_grid=local_grid_size,
+                             detection_thresh=detection_thresh)
     humans, scores = res.to_humans()[0]
     if draw is not None:
         return draw(image, humans, scores)
@@ -106,8 +126,12 @@ def inference(image, model: PoseProposalNet, outsize, local_grid_size, detection
 
 
 def inference_batch(frames_u8: torch.Tensor, model: PoseProposalNet, decoder: Optional[D.Decoder] = None,
-                    detection_thresh: float = 0.15) -> D.DecodeResult:
-    """Batched device-side inference: u8 [B,S,S,3] CUDA tensor -> compact people lists on the device."""
+                    detection_thresh: float = 0.15, flip_tta: bool = False, merger=None) -> D.DecodeResult:
+    """Batched device-side inference: u8 [B,S,S,3] CUDA tensor -> compact people lists on the device.
+    ``flip_tta=True``: flip-averaged heads (two forwards per image in one doubled batch; pass a Decoder and a
+    tta.FlipMerger as ``merger`` to allocate nothing per call)."""
+    if flip_tta:
+        return _decode_flip_averaged(frames_u8, model, decoder, detection_thresh, merger)
     unary, keys = model.forward_u8(frames_u8, fused_decode=True)     # the head tensor is never materialised
     if decoder is None:
         b, _, h, w = unary.shape
@@ -117,7 +141,7 @@ def inference_batch(frames_u8: torch.Tensor, model: PoseProposalNet, decoder: Op
 
 
 def inference_drawn(image, model: PoseProposalNet, outsize, local_grid_size, detection_thresh: float = 0.15,
-                    visbbox: bool = False, gridOn: bool = False):
+                    visbbox: bool = False, gridOn: bool = False, flip_tta: bool = False):
     """rt_test.py:87-147 including its last step (rt_test.py:135-147): the frame with the detected people drawn on it by
     the HIP rasteriser (render.py), as a PIL image -- a u8 [H,W,3] array where PIL is absent.  The people lists never
     leave the device; one frame goes up and one comes back."""
@@ -133,9 +157,12 @@ def inference_drawn(image, model: PoseProposalNet, outsize, local_grid_size, det
         if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
             raise ValueError("inference_drawn expects a uint8 HxWx3 RGB frame")
         frames = torch.from_numpy(np.ascontiguousarray(img)).unsqueeze(0).cuda(non_blocking=True)
-    head = model.forward_u8(frames)
-    res = D.decode_heads(head, insize_hw=(frames.shape[1], frames.shape[2]), local_grid=local_grid_size,
-                         detection_thresh=detection_thresh)
+    if flip_tta:
+        res = _decode_flip_averaged(frames, model, None, detection_thresh)
+    else:
+        head = model.forward_u8(frames)
+        res = D.decode_heads(head, insize_hw=(frames.shape[1], frames.shape[2]), local_grid=local_grid_size,
+                             detection_thresh=detection_thresh)
     drawn = R.draw_people(frames, res, visbbox=visbbox, gridOn=gridOn, outsize=outsize)[0].cpu().numpy()
     try:
         from PIL import Image
@@ -146,12 +173,12 @@ def inference_drawn(image, model: PoseProposalNet, outsize, local_grid_size, det
 
 def inference_batch_drawn(frames_u8: torch.Tensor, model: PoseProposalNet, decoder: Optional[D.Decoder] = None,
                           renderer=None, out: Optional[torch.Tensor] = None, detection_thresh: float = 0.15,
-                          visbbox: bool = False, gridOn: bool = False):
+                          visbbox: bool = False, gridOn: bool = False, flip_tta: bool = False, merger=None):
     """inference_batch plus the drawing, all on the device: u8 [B,S,S,3] CUDA frames -> (DecodeResult, drawn u8 frames).
     `out` as in render.Renderer (None: a new tensor, `frames_u8` itself: in place); pass a Decoder and a render.Renderer to
     allocate nothing per call."""
     from . import render as R
-    res = inference_batch(frames_u8, model, decoder, detection_thresh)
+    res = inference_batch(frames_u8, model, decoder, detection_thresh, flip_tta, merger)
     if renderer is None:
         renderer = R.Renderer(frames_u8.shape[0], res.max_humans, frames_u8.device)
     outW = frames_u8.shape[2] // 16

@@ -396,16 +396,18 @@ class PPNTrainer:
         self.base = total / n
         return self.base
 
-    def validate(self, batches, gt, max_humans: int = 64, detection_thresh: float = 0.15):
+    def validate(self, batches, gt, max_humans: int = 64, detection_thresh: float = 0.15, flip_tta: bool = False):
         """main.py:1017-1172: one validation epoch in EVAL mode over `batches`, an iterable of (x f32[b,3,H,W], image_index
         i32[b] -- rows of `gt`, a validate.GroundTruth -- and the targets dict or None); the first batch sets the batch
         size, a later one may be shorter.  Returns (losses.avg with the current task weights, the 8 AP values); nothing is
-        read back before the end (validate.Validator)."""
+        read back before the end (validate.Validator).  flip_tta: the decode sees the flip-averaged heads (tta.py); the loss
+        stays on the plain head."""
         from .validate import Validator
         net, v = self._eval_net(), None
         for x, image_index, targets in batches:
             if v is None:
-                v = Validator(net, gt, x.shape[0], self.criterion, self.task.w, detection_thresh, max_humans)
+                v = Validator(net, gt, x.shape[0], self.criterion, self.task.w, detection_thresh, max_humans,
+                              flip_tta=flip_tta)
                 v.reset()
             v.step(x, image_index, targets)
         if v is None:

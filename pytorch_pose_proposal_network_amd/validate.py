@@ -153,10 +153,15 @@ class Validator:
     eval losses when `targets` is given, Decoder.__call__ and match_people, and reads nothing back.  A last batch of fewer
     than `batch` images is padded here: its head rows beyond b are decoded but marked -1, and its loss is taken over the b
     images only.  An image_index of -1 inside a full batch skips that image's records (its loss still counts: leave such
-    images out of `targets` batches)."""
+    images out of `targets` batches).
+
+    flip_tta=True: horizontal-flip test-time averaging (tta.py).  The forward runs on the doubled batch [x | x mirrored]; the
+    loss stays on the plain head of x, and only the decode that feeds match_people sees the merged pair (ppn_tta_merge ->
+    Decoder.decode_fused)."""
 
     def __init__(self, net, gt: GroundTruth, batch: int, criterion=None, task_weights=None, detection_thresh: float = 0.15,
-                 max_humans: int = 64, nms_thresh: float = 0.3, min_num_keypoints: int = 1, dist_thresh: float = 0.5):
+                 max_humans: int = 64, nms_thresh: float = 0.3, min_num_keypoints: int = 1, dist_thresh: float = 0.5,
+                 flip_tta: bool = False):
         if getattr(net, "training", False):
             raise ValueError("Validator needs the network in eval mode (net.eval())")
         self.net, self.gt, self.batch, self.criterion = net, gt, int(batch), criterion
@@ -166,6 +171,10 @@ class Validator:
         self.decoder = D.Decoder(self.batch, (outH, outW), (inH, inW), net.local_grid_size, detection_thresh, nms_thresh,
                                  min_num_keypoints, max_humans, dev)
         self.records = Records(gt.n_images, max_humans, dev)
+        self.merger = None
+        if flip_tta:
+            from .tta import FlipMerger
+            self.merger = FlipMerger(self.batch, (outH, outW), net.local_grid_size, dev)
         self.task_weights = task_weights                     # read at finish(): the trainer's live tensor may be handed in
         self._x = torch.zeros(self.batch, 3, inH, inW, dtype=torch.float32, device=dev)
         self._index = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
@@ -192,6 +201,8 @@ class Validator:
             self._index[:b].copy_(index)
             self._index[b:].fill_(-1)
             x, index = self._x, self._index
+        if self.merger is not None:                          # [x | x mirrored] straight into the plan's input of batch 2B
+            x = self.merger.stage(x, out=self.net.input_buffer(2 * self.batch, x.shape[2], x.shape[3], u8=False))
         head = self.net(x)
         if targets is not None:
             if self.criterion is None:
@@ -199,7 +210,10 @@ class Validator:
             losses, _ = self.criterion.forward_backward(head[:b], targets, want_grad=False)
             self._loss_sum.add_(losses.double(), alpha=b)
             self._seen.add_(b)
-        result = self.decoder(head)
+        if self.merger is not None:
+            result = self.decoder.decode_fused(*self.merger.merge(head))
+        else:
+            result = self.decoder(head)
         torch.maximum(self._most_people, torch.where(index >= 0, result.count, 0).max().reshape(1), out=self._most_people)
         match_people(result, self.gt, index, self.records, self.dist_thresh)
 
