@@ -1151,6 +1151,7 @@ int ppn_bn_dual_bwd_streams_sum(const ppn_bn_bwd_desc* d, const void* xdot, floa
 }
 
 int ppn_add_relu(int32_t dtype, const void* z, const void* r, int64_t n, void* out, void* stream) {
+    if (n == 0) return PPN_OK;                           // an empty tensor has no storage: its pointers may be NULL
     if (!z || !r || !out || n < 0 || n % 8) return ppn::fail(PPN_E_INVALID, "ppn_add_relu: NULL pointer or n %% 8 != 0");
     long long blocks = (n / 8 + kThreads - 1) / kThreads;
     if (blocks > 256 * 16) blocks = 256 * 16;
@@ -1164,6 +1165,7 @@ int ppn_add_relu(int32_t dtype, const void* z, const void* r, int64_t n, void* o
 }
 
 int ppn_relu_mask(int32_t dtype, const void* out, const void* dout, const void* add, int64_t n, void* dz, void* stream) {
+    if (n == 0) return PPN_OK;
     if (!out || !dout || !dz || n < 0 || n % 8) return ppn::fail(PPN_E_INVALID, "ppn_relu_mask: NULL pointer or n %% 8 != 0");
     long long blocks = (n / 8 + kThreads - 1) / kThreads;
     if (blocks > 256 * 16) blocks = 256 * 16;
@@ -1254,9 +1256,9 @@ int ppn_image_to_nhwc(int32_t dtype, const float* src, int32_t batch, int32_t h,
 int ppn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr,
                   double beta1, double beta2, double eps, double weight_decay, int32_t step, float grad_scale,
                   void* param_lp, void* stream) {
-    if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || step < 1)
+    if (n < 0 || step < 1 || (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq)))
         return ppn::fail(PPN_E_INVALID, "ppn_adam_step: NULL buffer, n < 0 or step < 1");
-    if (n == 0) return PPN_OK;
+    if (n == 0) return PPN_OK;                           // an empty tensor has no storage: its pointers may be NULL
     float step_size, inv_bc2_sqrt;
     adam_consts(lr, beta1, beta2, step, &step_size, &inv_bc2_sqrt);
     long long blocks = (n + kThreads - 1) / kThreads;
@@ -1270,7 +1272,7 @@ int ppn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
 }
 
 int ppn_sumsq(const float* x, int64_t n, float* out, void* workspace, void* stream) {
-    if (!x || !out || !workspace || n < 0) return ppn::fail(PPN_E_INVALID, "ppn_sumsq: NULL argument");
+    if ((!x && n > 0) || !out || !workspace || n < 0) return ppn::fail(PPN_E_INVALID, "ppn_sumsq: NULL argument");
     long long blocks = (n + kThreads * 8 - 1) / (kThreads * 8);
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;

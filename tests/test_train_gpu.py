@@ -1,5 +1,6 @@
 """GPU parity of the training building blocks against plain PyTorch-CPU ops (what the reference's autograd /
-torch.optim.Adam / nn.BatchNorm2d execute: main.py:278-279, 643, 664-777)."""
+torch.optim.Adam / nn.BatchNorm2d execute: main.py:278-279, 643, 664-777).  The same kernels at their edges (block cap, offset and
+constant channels, the activation kink, per-element rounding bounds): tests/test_train_edges_gpu.py."""
 import numpy as np
 import pytest
 import torch
