@@ -565,6 +565,91 @@ int ppn_pckh_match(const int32_t* count, const int32_t* kp_cell, const float* bb
                    int32_t* rec_count, int32_t* flags, void* stream);
 
 /*
+ * Tracking people across the frames of a video on the device (no counterpart in the reference, whose rt_test.py treats every
+ * frame on its own), csrc/track.hip: the compact people lists of B = streams * frames images against up to PPN_TRACK_SLOTS
+ * resident tracks per stream, giving every person a track id that follows the human from frame to frame, and its keypoint
+ * centres smoothed over time.  tests/track_ref.py restates the rules below in NumPy; kernel and restatement agree on bytes.
+ *
+ * Batch layout: image b = s * frames + t is frame t of stream s.  The streams of a call are independent; the frames of a
+ * stream are processed in ascending t within the one call.  With n_frames given only t < n_frames[s] are processed (a
+ * negative n_frames[s] counts as 0); for every other image all out_id entries are -1, all out_hits entries 0, out_live is -1,
+ * out_xy is not written, and a stream without a processed frame leaves its state and its flags word untouched.
+ *
+ * Per processed image: P = min(max(count[b], 0), max_humans) and D = min(P, PPN_TRACK_MAX_DET); P > D sets
+ * PPN_TRACK_FLAG_DET_OVERFLOW and people p >= D take no part, nor does a person whose kp_cell[b][p][0] < 0.  Keypoint k of a
+ * person is present iff kp_cell[b][p][k] >= 0; its centre is x = (box[1] + box[3]) * 0.5f, y = (box[0] + box[2]) * 0.5f of
+ * its box (ymin, xmin, ymax, xmax).  The person's root box is bbox[b][p][0], its root score score[b][p][0].
+ *
+ * One frame, all comparisons on the state as it was before the frame, every f32 step one IEEE operation rounded on its own
+ * (no contraction, IEEE division):
+ *   1 pair values    for a live slot i (id != 0) and a person p: with the areas a = (ymax - ymin) * (xmax - xmin) of the two
+ *                    root boxes, tl = the larger ymin / xmin, br = the smaller ymax / xmax,
+ *                    inter = ((br0 - tl0) * (br1 - tl1)) * [tl0 < br0 && tl1 < br1] and iou = inter / ((a_i + a_p) - inter)
+ *                    as in ppn_nms; an iou that is not > 0 (a NaN included) counts as 0.0f.  r2 = (kp_gate * kp_gate) * a_i
+ *                    with a_i the TRACK's root area; n_close = the number of k in 1..K-1 present in both with
+ *                    dx * dx + dy * dy <= r2, dx = x_p - x_i, dy = y_p - y_i against the slot's stored (smoothed) centre.
+ *                    The pair is eligible iff iou >= iou_thr || n_close >= min_close.
+ *   2 match          for p = 0 .. D-1 ascending (descending root score): among the live slots not yet taken in this frame and
+ *                    eligible with p, the one with the largest n_close, then the largest iou, then the lowest index, is
+ *                    taken by p.
+ *   3 update         a taken slot: root = the person's root box; for every k in 0..K-1 present in the person,
+ *                    xy = old + alpha * (new - old) per coordinate if the slot had k and alpha != 1.0f, otherwise xy = new;
+ *                    mask = the person's presence bits (the centres of cleared bits stay as they are); miss = 0; hits += 1.
+ *   4 age            a live slot not taken: miss += 1, and when miss > max_age it is freed: id = mask = hits = miss = 0.
+ *   5 births         the unmatched participating people with root score >= birth_thr, in ascending p, take the free slots
+ *                    in ascending index (slots freed in step 4 included): id = ++last_id[s], root, mask and the centres of
+ *                    the present keypoints from the person (raw), hits = 1, miss = 0.  Without a free slot the person stays
+ *                    untracked and PPN_TRACK_FLAG_SLOT_OVERFLOW is set.  Ids are never reused.
+ *   6 outputs        out_id  i32 [B][max_humans]        the track id of person p, -1 for everyone else (untracked people,
+ *                                                       non-participants, rows >= P); every entry is written on every call
+ *                    out_hits i32 [B][max_humans]       the slot's hits after the frame, 0 where out_id is -1
+ *                    out_xy  f32 [B][max_humans][K][2]  or NULL; rows p < P only: a present keypoint of a tracked person
+ *                                                       gets the slot's stored centre (x, y), anyone else's present
+ *                                                       keypoint its raw centre, an absent keypoint (0, 0)
+ *                    out_live i32 [B]                   the number of live slots after the frame
+ *
+ *   count i32 [B], kp_cell i32 [B][max_humans][K], bbox f32 [B][max_humans][K][4] (16-byte aligned), score f32
+ *   [B][max_humans][K]: ppn_decode's outputs as they live on the device.
+ * One launch on `stream` (one workgroup per stream), no allocation, no host synchronisation, no D2H: the call can be captured
+ * into a graph.  No atomics -- each stream's workgroup owns its flags word, which it ORs into and the caller clears; two runs
+ * give identical bytes.  PPN_E_INVALID before anything is launched for: a NULL cfg, st, state pointer, input or required
+ * output; K outside 1..PPN_MAX_KP; min_close < 1; max_age < 0; a non-finite cfg value, iou_thr outside [0, 1], kp_gate < 0,
+ * alpha outside (0, 1]; streams, frames or max_humans < 1; a bbox that is not 16-byte aligned.  PPN_E_UNSUPPORTED:
+ * max_humans > PPN_MATCH_MAX_PEOPLE.  Precondition: the boxes are finite; otherwise the ids are unspecified, but no access
+ * leaves the buffers.
+ */
+#define PPN_TRACK_SLOTS 64            /* live tracks per stream: one lane each */
+#define PPN_TRACK_MAX_DET 256         /* people per image that take part */
+#define PPN_TRACK_FLAG_DET_OVERFLOW 1
+#define PPN_TRACK_FLAG_SLOT_OVERFLOW 2
+
+typedef struct ppn_track_cfg {
+    int32_t K;          /* keypoints, keypoint 0 = the instance (root) box      */
+    int32_t min_close;  /* >= 1                                                  */
+    int32_t max_age;    /* >= 0: frames a track survives unmatched               */
+    float iou_thr;      /* [0,1]                                                 */
+    float kp_gate;      /* >= 0: gate radius as a fraction of sqrt(track root area) */
+    float birth_thr;    /* root score a person needs to start a track            */
+    float alpha;        /* (0,1]: smoothing weight of the new observation        */
+} ppn_track_cfg;
+
+typedef struct ppn_track_state {      /* device pointers; ALL ZERO BYTES = a fresh tracker */
+    int32_t* id;      /* [S][64]   0 = free slot                                 */
+    int32_t* miss;    /* [S][64]                                                 */
+    int32_t* hits;    /* [S][64]                                                 */
+    uint32_t* mask;   /* [S][64]   bit k: keypoint k present                     */
+    float* root;      /* [S][64][4]   (ymin,xmin,ymax,xmax), raw                 */
+    float* xy;        /* [S][64][K][2] (x,y) centres, smoothed                   */
+    int32_t* last_id; /* [S]       ids handed out so far; the next id is ++last_id */
+    int32_t* flags;   /* [S]       OR of PPN_TRACK_FLAG_*, cleared by the caller  */
+} ppn_track_state;
+
+int ppn_track_update(const ppn_track_cfg* cfg, const ppn_track_state* st, const int32_t* count, const int32_t* kp_cell,
+                     const float* bbox, const float* score, int32_t streams, int32_t frames, int32_t max_humans,
+                     const int32_t* n_frames /* [S] or NULL = `frames` each */, int32_t* out_id, int32_t* out_hits,
+                     float* out_xy /* or NULL */, int32_t* out_live, void* stream);
+
+/*
  * Horizontal-flip test-time averaging (no counterpart in the reference), csrc/tta.hip: the network sees a frame and its
  * left-right mirror image, the second head is mapped back and averaged with the first, and only then the decode runs.
  * Geometry as in ppn_decode_cfg; the heads are f32 [batch, C, H, W] NCHW with C = 6K + E*sH*sW: six unary groups resp, conf,

@@ -54,6 +54,9 @@ SOURCES = [
     ("validate.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
     # tta.hip is bit-exact with NumPy's (a + b) * 0.5 in f32: the add and the multiply stay two IEEE operations
     ("tta.hip", ["-ffp-contract=off"]),
+    # track.hip is bit-exact with a NumPy restatement at the IoU and keypoint-gate thresholds: dx*dx + dy*dy and
+    # old + alpha * (new - old) uncontracted, the IoU's divide IEEE-rounded
+    ("track.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
 ]
 
 

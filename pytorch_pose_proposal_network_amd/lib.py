@@ -16,6 +16,8 @@ PPN_CONV_SPLIT_K = 16               # split-K pair of launches (csrc/conv_splitk
 PPN_ACT_NONE, PPN_ACT_RELU, PPN_ACT_LRELU, PPN_ACT_SIGMOID = 0, 1, 2, 3
 PPN_MATCH_JOINTS, PPN_MATCH_MAX_GT, PPN_MATCH_MAX_PEOPLE = 17, 64, 1024     # ppn_pckh_match (csrc/validate.hip)
 PPN_MATCH_FLAG_INDEX, PPN_MATCH_FLAG_GT_COUNT = 1, 2
+PPN_TRACK_SLOTS, PPN_TRACK_MAX_DET = 64, 256                                # ppn_track_update (csrc/track.hip)
+PPN_TRACK_FLAG_DET_OVERFLOW, PPN_TRACK_FLAG_SLOT_OVERFLOW = 1, 2
 PPN_STEM_RAW_S2 = 1 << 16          # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
 
 
@@ -121,6 +123,17 @@ class TtaCfg(C.Structure):
     """ppn_tta_cfg (csrc/tta.hip)."""
     _fields_ = [(n, C.c_int32) for n in ("K", "E", "sH", "sW", "H", "W")] + [
         ("kp_mirror", C.c_int32 * PPN_MAX_KP), ("edge_mirror", C.c_int32 * PPN_MAX_EDGES)]
+
+
+class TrackCfg(C.Structure):
+    """ppn_track_cfg (csrc/track.hip)."""
+    _fields_ = [("K", C.c_int32), ("min_close", C.c_int32), ("max_age", C.c_int32), ("iou_thr", C.c_float),
+                ("kp_gate", C.c_float), ("birth_thr", C.c_float), ("alpha", C.c_float)]
+
+
+class TrackState(C.Structure):
+    """ppn_track_state: device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in ("id", "miss", "hits", "mask", "root", "xy", "last_id", "flags")]
 
 
 class PPNError(RuntimeError):
@@ -264,6 +277,8 @@ _SIGNATURES.update({
                                  C.c_void_p, C.c_float] + [C.c_void_p] * 5),
     "ppn_tta_merge": (C.c_int, [C.POINTER(TtaCfg), C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4),
     "ppn_tta_stage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "ppn_track_update": (C.c_int, [C.POINTER(TrackCfg), C.POINTER(TrackState)] + [C.c_void_p] * 4 + [C.c_int32] * 3 +
+                         [C.c_void_p] * 6),
 })
 
 EXPORTS = tuple(_SIGNATURES)

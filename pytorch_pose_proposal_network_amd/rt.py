@@ -10,7 +10,8 @@ rt_test.py:109-120) and only the compact people list (<= 80 KB) comes back.  Web
 animation (rt_test.py:150-205) are out of scope.  ``inference`` returns the reference's ``(humans, scores)`` instead of a
 PIL image (pass ``draw=callable`` to post-process on the host); ``inference_drawn`` returns the drawn image as
 rt_test.inference does and ``inference_batch_drawn`` the drawn batch, both painted on the device (render.py,
-datatest.py:162-232).
+datatest.py:162-232).  ``inference_batch_tracked`` / ``inference_tracked`` add what the reference's loop lacks: ids that follow
+a person from frame to frame (track.py), again without reading the people lists back.
 """
 from __future__ import annotations
 
@@ -183,6 +184,42 @@ def inference_batch_drawn(frames_u8: torch.Tensor, model: PoseProposalNet, decod
         renderer = R.Renderer(frames_u8.shape[0], res.max_humans, frames_u8.device)
     outW = frames_u8.shape[2] // 16
     return res, renderer(frames_u8, res, visbbox=visbbox, gridOn=gridOn, out=out, outsize=(outW, frames_u8.shape[1] // 16))
+
+
+def inference_batch_tracked(frames_u8: torch.Tensor, model: PoseProposalNet, tracker, decoder: Optional[D.Decoder] = None,
+                            detection_thresh: float = 0.15, flip_tta: bool = False, merger=None):
+    """inference_batch plus the tracking, all on the device: u8 [B,S,S,3] CUDA frames with B = tracker.streams *
+    tracker.frames (image s * frames + t is frame t of stream s) -> (DecodeResult, track.TrackResult).  `tracker` is a
+    track.Tracker whose max_humans is the decoder's; it carries the tracks from call to call.  Nothing is read back."""
+    res = inference_batch(frames_u8, model, decoder, detection_thresh, flip_tta, merger)
+    return res, tracker.update(res)
+
+
+def inference_tracked(image, model: PoseProposalNet, outsize, local_grid_size, tracker, detection_thresh: float = 0.15,
+                      flip_tta: bool = False):
+    """``inference`` for the frames of one video: returns ``(humans, scores, ids)`` -- the reference-style lists of
+    ``inference`` and, per human, its track id (-1: untracked).  `tracker`: a track.Tracker(streams=1, frames=1,
+    max_humans=outsize[0] * outsize[1]) kept by the caller from frame to frame.  The humans' boxes are the frame's own;
+    the smoothed centres are ``tracker.xy[0]``."""
+    model.eval()
+    if isinstance(image, torch.Tensor) and image.is_cuda:
+        frames = image if image.dim() == 4 else image.unsqueeze(0)
+        if frames.dtype != torch.uint8 or frames.shape[0] != 1 or frames.shape[3] != 3:
+            raise ValueError("inference_tracked expects a uint8 [1,H,W,3] / [H,W,3] RGB frame")
+    else:
+        img = np.asarray(image)
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("inference_tracked expects a uint8 HxWx3 RGB frame")
+        frames = torch.from_numpy(np.ascontiguousarray(img)).unsqueeze(0).cuda(non_blocking=True)
+    if flip_tta:
+        res = _decode_flip_averaged(frames, model, None, detection_thresh)
+    else:
+        res = D.decode_heads(model.forward_u8(frames), insize_hw=(frames.shape[1], frames.shape[2]),
+                             local_grid=local_grid_size, detection_thresh=detection_thresh)
+    tracks = tracker.update(res, want_xy=True)
+    humans, scores = res.to_humans()[0]
+    ids = tracks.ids[0, :len(humans)].cpu().numpy().tolist()
+    return humans, scores, ids
 
 
 class InferencePipeline:
