@@ -28,6 +28,7 @@ NOSLP = ["-fno-slp-vectorize"]
 SOURCES = [
     ("abi.cpp", ["-x", "hip"]),
     ("decode.hip", ["-ffp-contract=off"]),
+    ("conv_route.cpp", []),   # host-only: which kernel a conv descriptor runs on
     ("conv.hip", NOSLP),
     ("conv_big.hip", NOSLP),
     ("conv_splitk.hip", NOSLP),

@@ -2,22 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
-#include "../../include/ppn.h"
+#include "error.h"
 
 namespace ppn {
 
-char* error_buffer();  // thread-local, 512 bytes
-
-inline int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(error_buffer(), 512, fmt, ap);
-    va_end(ap);
-    return code;
-}
+bool pack_tiled_enabled();   // abi.cpp
 
 #define PPN_HIP_CHECK(expr)                                                                      \
     do {                                                                                         \

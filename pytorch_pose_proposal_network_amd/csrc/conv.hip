@@ -18,7 +18,11 @@
 // which covers conv->BN->ReLU (drn.py:192-202), the pre-activation BasicBlock (drn.py:42-57: the
 // second output is the NEXT block's relu(bn1(x)), so zero padding happens after BN/ReLU as in the
 // reference), Bottleneck (drn.py:77-97) and the PPN neck/head incl. bias + sigmoid (model.py:113-134).
+//
+// Which kernel a descriptor runs on (this one, conv_big.hip, conv64.hip, conv_head.hip, conv_splitk.hip, stem3x3.hip) is decided
+// by conv_route.cpp; ppn::conv_launch below routes, then launches each segment of the route.
 #include "conv_common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -298,31 +302,13 @@ constexpr size_t conv_lds_bytes() {
     return stage > e ? stage : e;
 }
 
-struct TileChoice {
-    int bp, bc;
-};
-
-TileChoice choose_tile(int cout) {
-    if (cout <= 16) return {256, 16};
-    if (cout <= 32) return {256, 32};
-    if (cout <= 64) return {128, 64};
-    return {128, 128};
-}
-
 template <typename T, int BP, int BC, int WP, int WC>
-int launch_tile(const ConvKArgs& a, bool smallc, hipStream_t st, const char** kname) {
+int launch_tile(const ConvSegment& s, hipStream_t st) {
+    const ConvKArgs& a = s.args;
     const size_t lds = conv_lds_bytes<T, BP, BC>();
     const int grid = a.n_ctiles * a.n_ptiles;
-    // the name as rocprofv3 --kernel-trace prints it (a substring of the demangled symbol)
-    static char names[2][96];
-    if (!names[0][0]) {
-        for (int i = 0; i < 2; ++i)
-            snprintf(names[i], sizeof(names[i]), "conv_igemm_kernel<%s, %d, %d, %d, %d, %s>",
-                     elem_name<T>(), BP, BC, WP, WC, i ? "true" : "false");
-    }
-    if (smallc) {
+    if (s.smallc) {
         auto k = conv_igemm_kernel<T, BP, BC, WP, WC, true>;
-        if (kname) *kname = names[1];
         {
             static int max_lds_set = 0;   // the attribute sticks to the function: set it when it grows
             PPN_LDS_ONCE(max_lds_set, reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -331,7 +317,6 @@ int launch_tile(const ConvKArgs& a, bool smallc, hipStream_t st, const char** kn
         hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, a);
     } else {
         auto k = conv_igemm_kernel<T, BP, BC, WP, WC, false>;
-        if (kname) *kname = names[0];
         {
             static int max_lds_set = 0;   // the attribute sticks to the function: set it when it grows
             PPN_LDS_ONCE(max_lds_set, reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -344,17 +329,17 @@ int launch_tile(const ConvKArgs& a, bool smallc, hipStream_t st, const char** kn
 }
 
 template <typename T>
-int launch_dtype(const ConvKArgs& a, bool smallc, TileChoice tc, hipStream_t st, const char** kname) {
-    if (tc.bc == 16) return launch_tile<T, 256, 16, 4, 1>(a, smallc, st, kname);
-    if (tc.bc == 32) return launch_tile<T, 256, 32, 4, 1>(a, smallc, st, kname);
-    if (tc.bc == 64) return launch_tile<T, 128, 64, 2, 2>(a, smallc, st, kname);
-    return launch_tile<T, 128, 128, 2, 2>(a, smallc, st, kname);
+int launch_dtype(const ConvSegment& s, hipStream_t st) {
+    if (s.bc == 16) return launch_tile<T, 256, 16, 4, 1>(s, st);
+    if (s.bc == 32) return launch_tile<T, 256, 32, 4, 1>(s, st);
+    if (s.bc == 64) return launch_tile<T, 128, 64, 2, 2>(s, st);
+    return launch_tile<T, 128, 128, 2, 2>(s, st);
 }
 
-int ilog2_exact(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return (1 << l) == v ? l : -1;
+int launch_generic(const ConvSegment& s, hipStream_t st) {
+    if (s.dtype == PPN_F32) return launch_dtype<float>(s, st);
+    if (s.dtype == PPN_F16) return launch_dtype<_Float16>(s, st);
+    return launch_dtype<__bf16>(s, st);
 }
 
 // weight packing: [cout,cin,k,k] f32 -> [cout_pad][k_total] T with k = (ky*ks+kx)*cin + ci
@@ -575,231 +560,28 @@ extern "C" int ppn_pack_weight_x3(const float* w, int32_t cout, int32_t cin, int
     return PPN_OK;
 }
 
-namespace ppn {
-int conv_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname);
-int head_limb_launch(const ppn_conv_desc* d, long long m_lo, long long m_hi, hipStream_t st, const char** kname);
-bool conv64_supported(const ppn_conv_desc* d);
-int conv64_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname);
-int splitk_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname);   // conv_splitk.hip
-bool stem3x3_supported(int cin, int cout, int ksize, int stride, int dilation, int pad);
-int stem3x3_launch(int dtype, const void* src, int batch, int h, int w, int cout, int stride, const float* weight,
-                   const float* scale1, const float* shift1, const float* scale2, const float* shift2, void* out_raw,
-                   void* out_act, hipStream_t st, const char** kname);
-}
-
-extern "C" int ppn_conv_tiling(int32_t dtype, int32_t cin, int32_t cout, int32_t ksize, int32_t* k_step,
-                               int32_t* cout_tile, int32_t* k_order) {
-    if (dtype != PPN_F32 && dtype != PPN_BF16 && dtype != PPN_F16 && dtype != PPN_F16X3)
-        return ppn::fail(PPN_E_INVALID, "bad dtype %d", dtype);
-    if (cin < 1 || cout < 1 || ksize < 1) return ppn::fail(PPN_E_INVALID, "bad conv shape");
-    const int bk = dtype == PPN_F32 ? 32 : 64;
-    if (dtype == PPN_F16X3 && (cin % bk != 0 || cout < 64))
-        return ppn::fail(PPN_E_UNSUPPORTED, "PPN_F16X3 needs cin %% 64 == 0 and cout >= 64 (run the layer as PPN_F32)");
-    if (cin == 16 && (cout == 16 || cout == 32) && ksize == 3) {
-        // direct small-channel kernel (stem3x3.hip): weights stay in the reference layout, f32, unpadded
-        if (k_step) *k_step = 144;
-        if (cout_tile) *cout_tile = cout;
-        if (k_order) *k_order = 2;
-        return PPN_OK;
-    }
-    if (k_step) *k_step = bk;
-    BigTile bt;
-    const bool big = (cin % bk == 0) && big_tile_for(cout, 1, &bt);
-    // pad granularity = the LARGEST channel tile the launcher may pick for this Cout (it chooses per problem size)
-    if (cout_tile) *cout_tile = big ? (cout >= 256 ? 256 : (cout >= 128 ? 128 : 64)) : choose_tile(cout).bc;
-    if (k_order) *k_order = big ? 1 : 0;
-    return PPN_OK;
-}
-
-int ppn::conv_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname) {
-    if (!d) return ppn::fail(PPN_E_INVALID, "conv desc is NULL");
-    // opt-in split-K pair of launches (conv_splitk.hip): its own scope checks, never a fallback to the kernels below
-    if (d->flags & PPN_CONV_SPLIT_K) return ppn::splitk_launch(d, st, kname);
-    if (d->stats_mode != 0) {
-        // BatchNorm statistics from the epilogue: a request, not a demand -- *stats_tiles says whether this launch delivered
-        if (d->stats_mode < 1 || d->stats_mode > 2 || !d->stats_partial || !d->stats_tiles)
-            return ppn::fail(PPN_E_INVALID, "stats_mode 1 or 2 needs stats_partial and stats_tiles");
-        if (d->stats_mode == 2 && (!d->stats_x || !d->stats_gamma || !d->stats_beta || !d->stats_mean || !d->stats_rstd ||
-                                   d->stats_act < PPN_ACT_NONE || d->stats_act > PPN_ACT_LRELU))
-            return ppn::fail(PPN_E_INVALID, "stats_mode 2 needs stats_x, gamma, beta, mean, rstd and act none / relu / lrelu");
-        *d->stats_tiles = 0;
-    }
-    if (d->dtype != PPN_F32 && d->dtype != PPN_BF16 && d->dtype != PPN_F16 && d->dtype != PPN_F16X3)
-        return ppn::fail(PPN_E_INVALID, "bad dtype %d", d->dtype);
-    const bool x3 = d->dtype == PPN_F16X3;
-    const int bk = d->dtype == PPN_F32 ? 32 : 64, epc = d->dtype == PPN_F32 ? 4 : 8;
-    if (d->batch < 1 || d->in_h < 1 || d->in_w < 1 || d->cin < 1 || d->cout < 1)
-        return ppn::fail(PPN_E_INVALID, "bad conv geometry");
-    if (d->ksize < 1 || d->ksize > 5) return ppn::fail(PPN_E_UNSUPPORTED, "ksize %d not supported by the generic kernel", d->ksize);
-    if (d->cin % epc != 0) return ppn::fail(PPN_E_UNSUPPORTED, "cin %d must be a multiple of %d", d->cin, epc);
-    const int eff = d->dilation * (d->ksize - 1) + 1;
-    const int oh = (d->in_h + 2 * d->pad - eff) / d->stride + 1, ow = (d->in_w + 2 * d->pad - eff) / d->stride + 1;
-    if (oh != d->out_h || ow != d->out_w)
-        return ppn::fail(PPN_E_INVALID, "out size %dx%d inconsistent with %dx%d", d->out_h, d->out_w, oh, ow);
-    if (ppn::stem3x3_supported(d->cin, d->cout, d->ksize, d->stride, d->dilation, d->pad) && d->k_total == 144 &&
-        d->cout_pad == d->cout && !d->residual && !d->out_nchw_f32 &&
-        ((d->act1 == PPN_ACT_RELU && d->scale1 && d->shift1) ||
-         (d->act1 == PPN_ACT_NONE && !d->scale1 && !d->shift1 && !d->out_act)) &&
-        (!d->out_act || d->act2 == PPN_ACT_RELU)) {
-        if (!d->src || !d->weight) return ppn::fail(PPN_E_INVALID, "NULL src/weight");
-        if (oh != d->out_h || ow != d->out_w) return ppn::fail(PPN_E_INVALID, "inconsistent output size");
-        return ppn::stem3x3_launch(d->dtype, d->src, d->batch, d->in_h, d->in_w, d->cout, d->stride,
-                                   static_cast<const float*>(d->weight), d->scale1, d->shift1, d->scale2, d->shift2,
-                                   d->out_raw, d->out_act, st, kname);
-    }
-    const bool smallc = (d->cin % bk) != 0;
-    const int log2c = ilog2_exact(d->cin);
-    if (smallc && log2c < 0) return ppn::fail(PPN_E_UNSUPPORTED, "cin %d < K step must be a power of two", d->cin);
-    const int kreal = d->ksize * d->ksize * d->cin;
-    int kpad = ((kreal + bk - 1) / bk) * bk;
-    if (x3) {
-        if (smallc || d->cout < 64 || d->src2 || d->limb_edge_pad)
-            return ppn::fail(PPN_E_UNSUPPORTED, "PPN_F16X3: cin %% 64 == 0, cout >= 64, no fused shortcut, no edge tile");
-        kpad *= 3;                                                    // three virtual slabs per real one
-    }
-    const int kmain = kpad;
-    if (d->src2) {
-        if (d->cin2 < bk || d->cin2 % bk != 0 || d->stride2 < 1 || d->in2_h < 1 || d->in2_w < 1 || d->scale1 ||
-            d->out_nchw_f32 || smallc || (d->out_h - 1) * d->stride2 >= d->in2_h || (d->out_w - 1) * d->stride2 >= d->in2_w)
-            return ppn::fail(PPN_E_INVALID, "fused shortcut: cin2 must be a multiple of the K step, scale1 NULL, "
-                                            "and (out-1)*stride2 inside the second source");
-        kpad += d->cin2;
-    }
-    if (d->k_total != kpad) return ppn::fail(PPN_E_INVALID, "k_total %d != %d", d->k_total, kpad);
-    const long long m_all = (long long)d->batch * d->out_h * d->out_w;
-    if (m_all > 0x7fffffffLL) return ppn::fail(PPN_E_UNSUPPORTED, "tensor too large for 32-bit indexing");
-    long long m_lo = 0, m_hi = m_all;
-    if (d->m_count != 0) {
-        if (d->m_begin < 0 || d->m_count < 0 || (long long)d->m_begin + d->m_count > m_all)
-            return ppn::fail(PPN_E_INVALID, "pixel range [%d, +%d) outside the %lld output pixels", d->m_begin, d->m_count, m_all);
-        m_lo = d->m_begin; m_hi = m_lo + d->m_count;
-        // The NCHW f32 epilogues store four consecutive pixels of one channel plane as a float4 when HoWo % 4 == 0:
-        // a cut that is not a multiple of 4 would store misaligned, write up to 3 pixels of the neighbouring range
-        // (a race with the launch that owns it) or run into the next channel plane.
-        if (d->out_nchw_f32 && ((d->out_h * d->out_w) & 3) == 0 && ((m_lo & 3) != 0 || ((m_hi & 3) != 0 && m_hi != m_all)))
-            return ppn::fail(PPN_E_INVALID, "NCHW output: pixel range [%d, +%d) must begin on a multiple of 4 and end on one "
-                                            "(or at the last pixel)", d->m_begin, d->m_count);
-    } else if (!smallc && d->stats_mode == 0) {
-        // whole tensor: two launches with different tiles where that saves a round of workgroups (ppn_conv_split)
-        const long long cut = big_split_for(d->cout, m_all);
-        if (cut > 0 && cut < m_all) {
-            ppn_conv_desc part = *d;
-            part.m_begin = 0; part.m_count = (int32_t)cut;
-            const int rc = ppn::conv_launch(&part, st, kname);
-            if (rc != PPN_OK) return rc;
-            part.m_begin = (int32_t)cut; part.m_count = (int32_t)(m_all - cut);
-            return ppn::conv_launch(&part, st, nullptr);
+// Route the descriptor (conv_route.cpp decides everything), then launch what the route says.
+int ppn::conv_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname, int* strip) {
+    ConvRoute r;
+    const int rc = conv_route(d, knobs(), &r);
+    // BatchNorm statistics are a request, not a demand: *stats_tiles says whether this launch delivers them
+    if (r.stats_asked) *d->stats_tiles = rc == PPN_OK ? r.seg[0].stats_tiles : 0;
+    if (rc != PPN_OK) return rc;
+    if (kname) *kname = kernel_name(r.seg[0]);
+    if (strip) *strip = route_strip(r);
+    for (int i = 0; i < r.n; ++i) {
+        const ConvSegment& s = r.seg[i];
+        int lrc = PPN_OK;
+        switch (s.kernel) {
+            case Kernel::Stem3x3: lrc = ppn::stem3x3_launch(d, st); break;
+            case Kernel::Conv64: lrc = ppn::conv64_launch(d, st); break;
+            case Kernel::HeadLimb: lrc = ppn::head_limb_launch(d, s, st); break;
+            case Kernel::SplitK: lrc = ppn::splitk_launch(d, s, st); break;
+            case Kernel::Big: lrc = launch_big(s, st); break;
+            case Kernel::Generic: lrc = launch_generic(s, st); break;
         }
+        if (lrc != PPN_OK) return lrc;
     }
-    // 64 -> 64 3x3 stride 1 in the 16-bit modes: the register-resident filter bank kernel (conv64.hip), same results
-    if (ppn::conv64_supported(d) && d->in_h == d->out_h && d->in_w == d->out_w && !(d->flags & PPN_CONV_OUT_BF16))
-        return ppn::conv64_launch(d, st, kname);
-    const long long m = m_hi - m_lo;                                  // pixels of THIS launch: the tile is chosen for them
-    TileChoice tc = choose_tile(d->cout);
-    BigTile bt{0, 0};
-    const bool big = !smallc && big_tile_for(d->cout, m, &bt, kpad / bk, (d->flags & PPN_CONV_SHARED_GPU) != 0);
-    if (d->limb_edge_pad != 0) {
-        // edge-aligned limb tile (conv_head.hip): rows [e * limb_edge_pad, +limb_window) of the packed weight / shift1
-        // hold edge e's window, the rest of each edge's rows are padding
-        if (d->limb_edge_pad != kEdgeTileBC || smallc || d->src2 || !d->argmax_keys || !d->out_nchw_f32 || d->out_raw ||
-            d->unary_out || d->unary_channels != 0 || d->residual || d->out_act || d->limb_window < 1 ||
-            d->limb_window > d->limb_edge_pad || d->cout % d->limb_window != 0 ||
-            d->cout_pad != d->cout / d->limb_window * d->limb_edge_pad || d->act1 != PPN_ACT_SIGMOID)
-            return ppn::fail(PPN_E_INVALID, "limb_edge_pad: needs %d rows per edge (window <= that), cout = E * window, "
-                                            "cout_pad = E * limb_edge_pad, sigmoid, argmax_keys only (no out_raw / unary_out)",
-                             kEdgeTileBC);
-        if (!d->src || !d->weight) return ppn::fail(PPN_E_INVALID, "NULL src/weight");
-        return ppn::head_limb_launch(d, m_lo, m_hi, st, kname);
-    }
-    const int bc = big ? bt.bc : tc.bc, bp = big ? bt.bp : tc.bp;
-    if (d->cout_pad % bc != 0 || d->cout_pad < d->cout)
-        return ppn::fail(PPN_E_INVALID, "cout_pad %d must be a multiple of %d and >= cout", d->cout_pad, bc);
-    if (!d->src || !d->weight || !d->zero_page) return ppn::fail(PPN_E_INVALID, "NULL src/weight/zero_page");
-    if (!d->out_raw && !d->out_act && !d->argmax_keys) return ppn::fail(PPN_E_INVALID, "conv has no output");
-    if (d->argmax_keys && !d->limb_edge_pad &&
-        (!d->out_nchw_f32 || !d->unary_out || d->unary_channels < 0 || d->limb_window < 1 ||
-         d->unary_channels > d->cout || (d->cout - d->unary_channels) % d->limb_window != 0))
-        return ppn::fail(PPN_E_INVALID, "fused arg-max needs the NCHW head mode, unary_out and cout = unary + E*window");
-    if (d->argmax_keys && d->act1 != PPN_ACT_SIGMOID)
-        return ppn::fail(PPN_E_INVALID, "fused arg-max keys assume non-negative (sigmoid) outputs");
-    if (!d->out_nchw_f32 && (d->act1 == PPN_ACT_SIGMOID || d->act2 == PPN_ACT_SIGMOID))
-        return ppn::fail(PPN_E_UNSUPPORTED, "sigmoid is only implemented for the NCHW head output");
-    if (d->out_nchw_f32) {
-        if (d->residual || d->out_act || (!d->out_raw && !d->argmax_keys))
-            return ppn::fail(PPN_E_UNSUPPORTED, "NCHW head output supports out_raw / fused arg-max only");
-    } else if (d->cout % 8 != 0) {
-        return ppn::fail(PPN_E_UNSUPPORTED, "NHWC output needs cout %% 8 == 0 (got %d)", d->cout);
-    }
-    const long long in_elems = (long long)d->batch * d->in_h * d->in_w * d->cin * (x3 ? 2 : 1);
-    if (in_elems > 0x7fffffffLL) return ppn::fail(PPN_E_UNSUPPORTED, "tensor too large for 32-bit indexing");
-    ConvKArgs a;
-    a.src = static_cast<const char*>(d->src);
-    a.wgt = static_cast<const char*>(d->weight);
-    a.scale1 = d->scale1; a.shift1 = d->shift1;
-    a.residual = static_cast<const char*>(d->residual);
-    a.out_raw = static_cast<char*>(d->out_raw);
-    a.scale2 = d->scale2; a.shift2 = d->shift2;
-    a.out_act = static_cast<char*>(d->out_act);
-    a.zero = static_cast<const char*>(d->zero_page);
-    a.B = d->batch; a.H = d->in_h; a.W = d->in_w; a.Cin = x3 ? 2 * d->cin : d->cin; a.Ho = d->out_h; a.Wo = d->out_w; a.Cout = d->cout;
-    a.ks = d->ksize; a.stride = d->stride; a.dil = d->dilation; a.pad = d->pad;
-    a.Ktot = d->k_total; a.M = (int)m_hi; a.m_base = (int)m_lo; a.HoWo = d->out_h * d->out_w;
-    a.div_howo = make_fastdiv((unsigned)a.HoWo); a.div_wo = make_fastdiv((unsigned)d->out_w);
-    a.act1 = d->act1; a.act2 = d->act2; a.nchw = d->out_nchw_f32;
-    a.log2Cin = log2c < 0 ? 0 : log2c;
-    a.n_ctiles = d->cout_pad / bc;
-    a.div_nct = make_fastdiv((unsigned)a.n_ctiles);
-    a.n_ptiles = (int)((m + bp - 1) / bp);
-    a.src2 = static_cast<const char*>(d->src2);
-    a.H2 = d->src2 ? d->in2_h : 1; a.W2 = d->src2 ? d->in2_w : 1; a.Cin2 = d->src2 ? d->cin2 : 0;
-    a.stride2 = d->src2 ? d->stride2 : 1;
-    a.nsteps_main = kmain / bk;
-    a.src2_bytes = d->src2 ? (unsigned)((size_t)d->batch * d->in2_h * d->in2_w * d->cin2 * (d->dtype == PPN_F32 ? 4 : 2)) : 0u;
-    if (d->src2 && (size_t)d->batch * d->in2_h * d->in2_w * d->cin2 * 4 >= 0x7fffff00ull)
-        return ppn::fail(PPN_E_UNSUPPORTED, "second source too large for the buffer-addressed conv kernel");
-    a.unary_out = d->unary_out;
-    a.amax_keys = reinterpret_cast<unsigned long long*>(d->argmax_keys);
-    a.unary_ch = d->unary_channels;
-    a.window = d->limb_window;
-    a.lo_off = x3 ? d->cin * 2 : 0;                                   // source pixel = [hi(cin) | lo'(cin)] halves
-    a.out_plain = (d->flags & PPN_CONV_X3_PLAIN_OUT) ? 1 : 0;
-    if (a.out_plain && (!x3 || d->out_nchw_f32))
-        return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_X3_PLAIN_OUT: a PPN_F16X3 launch with NHWC outputs");
-    a.pf_ptr = static_cast<const char*>(d->prefetch);
-    a.pf_lines = (d->prefetch && d->prefetch_bytes > 0) ? (unsigned)std::min<long long>(d->prefetch_bytes / 128, 1 << 24) : 0u;
-    a.pf_per_wg = 0;                                                  // set by launch_big (it knows the grid)
-    a.out_bf16 = (d->flags & PPN_CONV_OUT_BF16) ? 1 : 0;
-    a.st_partial = nullptr; a.st_mode = 0; a.st_act = 0; a.st_x = nullptr;
-    a.st_gamma = a.st_beta = a.st_mean = a.st_rstd = nullptr;
-    a.sp_rows = a.sp_pitch = 0; a.sp_div = make_fastdiv(1);          // set by launch_big
-    if (d->stats_mode != 0 && big && big_stats_ok(d->dtype, bt) && !d->out_nchw_f32 && !d->residual && !d->out_act && d->out_raw &&
-        d->cout % 8 == 0 && !a.out_bf16 && !d->src2 && !d->argmax_keys && d->m_count == 0 && a.n_ptiles <= 1024) {
-        // the conditions of the single-output 16-bit epilogue (conv_big.hip `fast`) + one launch over the whole tensor +
-        // no more pixel tiles than a BatchNorm workspace has partial blocks (train.hip kMaxBlocks)
-        a.st_partial = static_cast<double*>(d->stats_partial);
-        a.st_mode = d->stats_mode; a.st_act = d->stats_act;
-        a.st_x = static_cast<const char*>(d->stats_x);
-        a.st_gamma = d->stats_gamma; a.st_beta = d->stats_beta; a.st_mean = d->stats_mean; a.st_rstd = d->stats_rstd;
-        *d->stats_tiles = a.n_ptiles;
-    }
-    if (a.out_bf16 && (d->dtype != PPN_F16 || !big || d->out_nchw_f32))
-        return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_OUT_BF16: a PPN_F16 launch of the large-tile kernel with NHWC outputs");
-    if (x3 && !big) return ppn::fail(PPN_E_UNSUPPORTED, "PPN_F16X3 is implemented by the large-tile kernel only");
-    if (big) return launch_big(a, d->dtype, bt, st, kname);
-    if (d->argmax_keys) return ppn::fail(PPN_E_UNSUPPORTED, "fused arg-max is implemented by the large-tile kernel only");
-    if (d->src2) return ppn::fail(PPN_E_UNSUPPORTED, "the fused shortcut is implemented by the large-tile kernel only");
-    if (d->dtype == PPN_F32) return launch_dtype<float>(a, smallc, tc, st, kname);
-    if (d->dtype == PPN_F16) return launch_dtype<_Float16>(a, smallc, tc, st, kname);
-    return launch_dtype<__bf16>(a, smallc, tc, st, kname);
-}
-
-extern "C" int ppn_conv_split(int32_t dtype, int32_t cin, int32_t cout, int64_t m, int64_t* m_split) {
-    if (dtype != PPN_F32 && dtype != PPN_BF16 && dtype != PPN_F16 && dtype != PPN_F16X3)
-        return ppn::fail(PPN_E_INVALID, "bad dtype %d", dtype);
-    if (cin < 1 || cout < 1 || m < 1 || !m_split) return ppn::fail(PPN_E_INVALID, "ppn_conv_split: bad arguments");
-    const int bk = dtype == PPN_F32 ? 32 : 64;
-    const long long cut = (cin % bk == 0) ? big_split_for(cout, m) : 0;
-    *m_split = (cut > 0 && cut < m) ? cut : 0;
     return PPN_OK;
 }
 
@@ -808,10 +590,10 @@ static thread_local int g_last_conv_strip = 0;
 
 extern "C" int ppn_conv2d_fused(const ppn_conv_desc* d, void* stream) {
     const char* kn = nullptr;
-    ppnconv::g_last_strip = 0;
-    const int rc = ppn::conv_launch(d, static_cast<hipStream_t>(stream), &kn);
+    int strip = 0;
+    const int rc = ppn::conv_launch(d, static_cast<hipStream_t>(stream), &kn, &strip);
     if (rc == PPN_OK && kn) g_last_conv_kernel = kn;
-    g_last_conv_strip = rc == PPN_OK ? ppnconv::g_last_strip : g_last_conv_strip;
+    if (rc == PPN_OK) g_last_conv_strip = strip;
     return rc;
 }
 
@@ -894,8 +676,7 @@ extern "C" int ppn_pack_table_build(const ppn_pack_item* items, int32_t n, void*
         d.kstep = s.k_step > 0 ? s.k_step : 1; d.transposed = s.transposed ? 1 : 0;
         d.otype = (s.k_order == 2 || s.dtype == PPN_F32) ? 0 : (s.dtype == PPN_BF16 ? 1 : 2);   // k_order 2 stays f32
         d.first_block = (int)blocks;
-        static const bool tiles_on = !(getenv("PPN_PACK_TILED") && atoi(getenv("PPN_PACK_TILED")) == 0);   // A/B switch
-        d.tiled = (tiles_on && d.korder == 1 && d.kstep == 64 && d.cin % 64 == 0 && d.ktot == d.ntaps * d.cin &&
+        d.tiled = (ppn::pack_tiled_enabled() && d.korder == 1 && d.kstep == 64 && d.cin % 64 == 0 && d.ktot == d.ntaps * d.cin &&
                    d.ntaps <= kTileMaxTaps && d.otype != 0 && s.cout_pad % kTileRows == 0) ? 1 : 0;
         blocks += d.tiled ? (long long)(s.cout_pad / kTileRows) * (d.cin / 64)
                           : (long long)((d.n + kPackChunk - 1) / kPackChunk);

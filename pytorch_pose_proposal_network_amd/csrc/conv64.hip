@@ -23,6 +23,7 @@
 #include <utility>
 
 #include "conv_common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -294,20 +295,9 @@ __global__ void __launch_bounds__(256, 2) conv64_kernel(C64Args a, unsigned src_
 
 namespace ppn {
 
-static int g_conv64_on = -1;             // -1: not decided yet (PPN_CONV64=0 in the environment disables it)
-
-bool conv64_supported(const ppn_conv_desc* d) {
-    if (g_conv64_on < 0) g_conv64_on = (getenv("PPN_CONV64") && atoi(getenv("PPN_CONV64")) == 0) ? 0 : 1;
-    if (!g_conv64_on || (d->flags & PPN_CONV_NO_FILTER_BANK)) return false;
-    return (d->dtype == PPN_BF16 || d->dtype == PPN_F16) && d->cin == 64 && d->cout == 64 && d->ksize == 3 && d->stride == 1 &&
-           d->dilation == 1 && d->pad == 1 && !d->src2 && !d->out_nchw_f32 && !d->argmax_keys && d->k_total == 576 &&
-           d->cout_pad == 64 && d->m_count == 0 && d->act1 != PPN_ACT_SIGMOID && d->act2 != PPN_ACT_SIGMOID;
-}
-
-int conv64_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname) {
-    if (!d->src || !d->weight || (!d->out_raw && !d->out_act)) return ppn::fail(PPN_E_INVALID, "conv64: NULL src/weight/output");
+// the scope test (64 -> 64, 3x3, stride 1, 16-bit) and the descriptor checks are conv_route.cpp's
+int conv64_launch(const ppn_conv_desc* d, hipStream_t st) {
     const size_t src_bytes = (size_t)d->batch * d->in_h * d->in_w * 64 * 2;
-    if (src_bytes >= 0x7fffff00ull) return ppn::fail(PPN_E_UNSUPPORTED, "tensor too large for the buffer-addressed conv kernel");
     C64Args a;
     a.src = static_cast<const char*>(d->src);
     a.wgt = static_cast<const char*>(d->weight);
@@ -318,7 +308,6 @@ int conv64_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname) {
     a.B = d->batch; a.H = d->in_h; a.W = d->in_w; a.act1 = d->act1; a.act2 = d->act2;
     a.tiles_x = (d->in_w + TW - 1) / TW; a.tiles_y = (d->in_h + TH - 1) / TH;
     const long long nt = (long long)d->batch * a.tiles_x * a.tiles_y;
-    if (nt > 0x7fffffffLL) return ppn::fail(PPN_E_UNSUPPORTED, "too many tiles");
     a.n_tiles = (int)nt;
     a.div_tx = make_fastdiv((unsigned)a.tiles_x);
     a.div_tpi = make_fastdiv((unsigned)(a.tiles_x * a.tiles_y));
@@ -334,18 +323,11 @@ int conv64_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname) {
         PPN_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     }
     const int grid = (int)std::min<long long>(nt, 2LL * n_cu);      // persistent: two workgroups per CU
-    static char names[2][48];
-    if (!names[0][0]) {
-        snprintf(names[0], sizeof(names[0]), "conv64_kernel<__bf16>");
-        snprintf(names[1], sizeof(names[1]), "conv64_kernel<_Float16>");
-    }
     if (d->dtype == PPN_F16) {
-        if (kname) *kname = names[1];
         static int set16 = 0;
         PPN_LDS_ONCE(set16, reinterpret_cast<const void*>(conv64_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         hipLaunchKernelGGL(conv64_kernel<_Float16>, dim3(grid), dim3(256), LDS_BYTES, st, a, (unsigned)src_bytes);
     } else {
-        if (kname) *kname = names[0];
         static int setb = 0;
         PPN_LDS_ONCE(setb, reinterpret_cast<const void*>(conv64_kernel<__bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         hipLaunchKernelGGL(conv64_kernel<__bf16>, dim3(grid), dim3(256), LDS_BYTES, st, a, (unsigned)src_bytes);
@@ -355,8 +337,3 @@ int conv64_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname) {
 }
 
 }  // namespace ppn
-
-extern "C" int ppn_set_conv64_enabled(int32_t on) {
-    ppn::g_conv64_on = on ? 1 : 0;
-    return PPN_OK;
-}

@@ -13,7 +13,8 @@
 //   loads      buffer_load ... lds (LDS-DMA) through raw buffer descriptors: per-lane 32-bit offsets, the
 //              K-step offset of the weight stream in SGPRs, and padded taps expressed as an OUT-OF-RANGE
 //              offset, which the hardware range check turns into zeros in LDS (tools/probes/buf_lds_oob.hip)
-// BP is picked per layer so that the number of workgroups is close to a multiple of the 256 CUs.
+// BP is picked per layer so that the number of workgroups is close to a multiple of the 256 CUs (conv_route.cpp: the tile, the
+// strip loader and the statistics epilogue of a launch are decided there; the host code at the end of this file only launches).
 // K loop: two named fragment sets; the MFMAs of one set cover the LDS reads of the other and the DMA issue
 // of the next stage, so the matrix pipe restarts immediately after the per-step barrier.
 // Epilogue through LDS in 64-pixel (NHWC) / 64-channel (NCHW head) chunks: 16-byte coalesced stores.  The head
@@ -25,16 +26,11 @@
 #include <utility>
 
 #include "conv_common.h"
+#include "launchers.h"
 
 namespace {
 
 using namespace ppnconv;
-
-// the tiles whose single-output 16-bit epilogue exists (the whole tile as 16-bit rows in the staging LDS) AND that carry the
-// BatchNorm-statistics instantiation: kFastFits of the kernel, restated for the host
-constexpr bool stats_tile_ok(int bp, int bc) {
-    return bc >= 128 && (size_t)bp * (size_t)(bc * 2 + 16) <= 2 * (size_t)(bp + bc) * 128;
-}
 
 // Build-time diagnostics (tools/build_variant.py NAME conv_big.hip -DPPN_DIAG=n): TIMING ONLY, results are wrong.
 //   1 = no wait for the DMA, 2 = no DMA in the K loop, 3 = 32x32x16 MFMAs (half the MFMA issue slots) on the same reads,
@@ -1104,14 +1100,9 @@ conv_igemm_big_kernel(ConvKArgs a, unsigned src_bytes, unsigned wgt_bytes) {
 }
 
 template <typename T, int BP, int BC, int NW, bool SC, bool X3 = false, bool ST = false, bool SP = false>
-int launch_sc(const ConvKArgs& a, hipStream_t st, const char** kname) {
-    // SP: two 256-row strip buffers instead of the two activation stages; the reported name stays the tile's
+int launch_sc(const ConvKArgs& a, hipStream_t st) {
+    // SP: two 256-row strip buffers instead of the two activation stages
     constexpr size_t lds = SP ? 2 * (size_t)(256 + BC) * 128 : 2 * (size_t)(BP + BC) * 128;
-    static char name[96];
-    if (!name[0])
-        snprintf(name, sizeof(name), "conv_igemm_big_kernel<%s, %d, %d, %d, %s%s>", elem_name<T>(),
-                 BP, BC, NW, SC ? "true" : "false", X3 ? ", true" : (ST ? ", false, true" : ""));
-    if (kname) *kname = name;
     const size_t src_bytes = (size_t)a.B * a.H * a.W * a.Cin * sizeof(T);
     const size_t wgt_bytes = (size_t)a.n_ctiles * BC * a.Ktot * sizeof(T);
     auto k = conv_igemm_big_kernel<T, BP, BC, NW, SC, X3, ST, SP>;
@@ -1120,269 +1111,84 @@ int launch_sc(const ConvKArgs& a, hipStream_t st, const char** kname) {
         PPN_LDS_ONCE(max_lds_set, reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lds);
     }
-    ConvKArgs b = a;
-    if (b.pf_lines) {                                  // prefetch hint: lines per workgroup, at most two per thread
-        const unsigned nwg = (unsigned)(a.n_ctiles * a.n_ptiles);
-        b.pf_per_wg = std::min<unsigned>((b.pf_lines + nwg - 1) / nwg, 2u * 64 * NW);
-    }
-    hipLaunchKernelGGL(k, dim3(a.n_ctiles * a.n_ptiles), dim3(64 * NW), lds, st, b, (unsigned)src_bytes,
+    hipLaunchKernelGGL(k, dim3(a.n_ctiles * a.n_ptiles), dim3(64 * NW), lds, st, a, (unsigned)src_bytes,
                        (unsigned)wgt_bytes);
     PPN_LAUNCH_CHECK();
     return PPN_OK;
 }
 
+// The ladders below switch on the segment's fields (conv_route.cpp chose them); the `if constexpr` guards only keep
+// combinations that have no instantiation from being compiled -- the route never asks for one.
 template <typename T, int BP, int BC, int NW>
-int launch_one(const ConvKArgs& a, hipStream_t st, const char** kname) {
-    if constexpr (NW == 8 && BC >= 128) {
-        if (a.src2) return launch_sc<T, BP, BC, NW, true>(a, st, kname);
-    } else {
-        if (a.src2) return ppn::fail(PPN_E_UNSUPPORTED, "fused shortcut needs the 8-wave 128/256-channel tiles");
+int launch_one(const ConvSegment& s, hipStream_t st) {
+    if (s.shortcut) {
+        if constexpr (NW == 8 && BC >= 128) return launch_sc<T, BP, BC, NW, true>(s.args, st);
+        else return ppn::fail(PPN_E_UNSUPPORTED, "fused shortcut: no such instantiation of the large-tile kernel");
     }
-    if (a.st_mode != 0) {                              // conv_launch only asks where stats_tile_ok() said yes
+    if (s.stats) {
         if constexpr (std::is_same<T, __bf16>::value && NW == 8 && stats_tile_ok(BP, BC))
-            return launch_sc<T, BP, BC, NW, false, false, true>(a, st, kname);
+            return launch_sc<T, BP, BC, NW, false, false, true>(s.args, st);
         else
             return ppn::fail(PPN_E_UNSUPPORTED, "BatchNorm statistics: no such instantiation of the large-tile kernel");
     }
-    if constexpr (sizeof(T) == 2 && BP == 192 && BC == 256 && NW == 8) {
-        if (a.sp_rows > 0) return launch_sc<T, BP, BC, NW, false, false, false, true>(a, st, kname);
+    if (s.strip) {
+        if constexpr (sizeof(T) == 2 && BP == 192 && BC == 256 && NW == 8)
+            return launch_sc<T, BP, BC, NW, false, false, false, true>(s.args, st);
+        else
+            return ppn::fail(PPN_E_UNSUPPORTED, "strip loader: no such instantiation of the large-tile kernel");
     }
-    return launch_sc<T, BP, BC, NW, false>(a, st, kname);
-}
-
-int conv_waves() {
-    static const int nw = getenv("PPN_CONV_WAVES") ? atoi(getenv("PPN_CONV_WAVES")) : 8;   // tuning knob
-    return nw;
+    return launch_sc<T, BP, BC, NW, false>(s.args, st);
 }
 
 template <typename T>
-int launch_T(const ConvKArgs& a, BigTile t, hipStream_t st, const char** kname) {
-    const int nw = conv_waves();
-    if (nw == 4 && t.bp != 144) {
-        if (t.bc == 256) {
-            if (t.bp == 256) return launch_one<T, 256, 256, 4>(a, st, kname);
-            if (t.bp == 192) return launch_one<T, 192, 256, 4>(a, st, kname);
-            return launch_one<T, 128, 256, 4>(a, st, kname);
+int launch_T(const ConvSegment& s, hipStream_t st) {
+    if (s.nw == 4) {
+        if (s.bc == 256) {
+            if (s.bp == 256) return launch_one<T, 256, 256, 4>(s, st);
+            if (s.bp == 192) return launch_one<T, 192, 256, 4>(s, st);
+            return launch_one<T, 128, 256, 4>(s, st);
         }
-        if (t.bp == 256) return launch_one<T, 256, 128, 4>(a, st, kname);
-        if (t.bp == 192) return launch_one<T, 192, 128, 4>(a, st, kname);
-        return launch_one<T, 128, 128, 4>(a, st, kname);
+        if (s.bp == 256) return launch_one<T, 256, 128, 4>(s, st);
+        if (s.bp == 192) return launch_one<T, 192, 128, 4>(s, st);
+        return launch_one<T, 128, 128, 4>(s, st);
     }
-    if (t.bc == 256) {
-        if (t.bp == 256) return launch_one<T, 256, 256, 8>(a, st, kname);
-        if (t.bp == 192) return launch_one<T, 192, 256, 8>(a, st, kname);
-        if (t.bp == 144) return launch_one<T, 144, 256, 8>(a, st, kname);
-        return launch_one<T, 128, 256, 8>(a, st, kname);
+    if (s.bc == 256) {
+        if (s.bp == 256) return launch_one<T, 256, 256, 8>(s, st);
+        if (s.bp == 192) return launch_one<T, 192, 256, 8>(s, st);
+        if (s.bp == 144) return launch_one<T, 144, 256, 8>(s, st);
+        return launch_one<T, 128, 256, 8>(s, st);
     }
-    if (t.bc == 128) {
-        if (t.bp == 256) return launch_one<T, 256, 128, 8>(a, st, kname);
-        if (t.bp == 192) return launch_one<T, 192, 128, 8>(a, st, kname);
-        return launch_one<T, 128, 128, 8>(a, st, kname);
+    if (s.bc == 128) {
+        if (s.bp == 256) return launch_one<T, 256, 128, 8>(s, st);
+        if (s.bp == 192) return launch_one<T, 192, 128, 8>(s, st);
+        return launch_one<T, 128, 128, 8>(s, st);
     }
-    if (t.bp == 256) return launch_one<T, 256, 64, 8>(a, st, kname);
-    return launch_one<T, 128, 64, 8>(a, st, kname);
+    if (s.bp == 256) return launch_one<T, 256, 64, 8>(s, st);
+    return launch_one<T, 128, 64, 8>(s, st);
 }
 
 // split-f16 mode (PPN_F16X3): the 8-wave tiles, no fused shortcut
-int launch_X3(const ConvKArgs& a, BigTile t, hipStream_t st, const char** kname) {
-    if (a.src2) return ppn::fail(PPN_E_UNSUPPORTED, "PPN_F16X3: no fused shortcut");
-    if (t.bc == 256) {
-        if (t.bp == 256) return launch_sc<_Float16, 256, 256, 8, false, true>(a, st, kname);
-        if (t.bp == 192) return launch_sc<_Float16, 192, 256, 8, false, true>(a, st, kname);
-        if (t.bp == 144) return launch_sc<_Float16, 144, 256, 8, false, true>(a, st, kname);
-        return launch_sc<_Float16, 128, 256, 8, false, true>(a, st, kname);
+int launch_X3(const ConvSegment& s, hipStream_t st) {
+    const ConvKArgs& a = s.args;
+    if (s.bc == 256) {
+        if (s.bp == 256) return launch_sc<_Float16, 256, 256, 8, false, true>(a, st);
+        if (s.bp == 192) return launch_sc<_Float16, 192, 256, 8, false, true>(a, st);
+        if (s.bp == 144) return launch_sc<_Float16, 144, 256, 8, false, true>(a, st);
+        return launch_sc<_Float16, 128, 256, 8, false, true>(a, st);
     }
-    if (t.bc == 128) {
-        if (t.bp == 256) return launch_sc<_Float16, 256, 128, 8, false, true>(a, st, kname);
-        if (t.bp == 192) return launch_sc<_Float16, 192, 128, 8, false, true>(a, st, kname);
-        return launch_sc<_Float16, 128, 128, 8, false, true>(a, st, kname);
+    if (s.bc == 128) {
+        if (s.bp == 256) return launch_sc<_Float16, 256, 128, 8, false, true>(a, st);
+        if (s.bp == 192) return launch_sc<_Float16, 192, 128, 8, false, true>(a, st);
+        return launch_sc<_Float16, 128, 128, 8, false, true>(a, st);
     }
-    if (t.bp == 256) return launch_sc<_Float16, 256, 64, 8, false, true>(a, st, kname);
-    return launch_sc<_Float16, 128, 64, 8, false, true>(a, st, kname);
+    if (s.bp == 256) return launch_sc<_Float16, 256, 64, 8, false, true>(a, st);
+    return launch_sc<_Float16, 128, 64, 8, false, true>(a, st);
 }
 
 }  // namespace
 
-namespace ppnconv {
-
-// Pick the tile: channels 256 / 128 / 64 by Cout, pixel height so that the fewest CU-rounds are wasted
-// (256 CUs; one workgroup per CU, two for the 64-channel tile whose LDS footprint is 80 KB).
-// PPN_CONV_TILE="bp,bc" overrides the choice for every eligible layer (tuning knob).
-static int g_tile_policy = getenv("PPN_CONV_CONT") ? 1 : 0;
-// forced tile (ppn_set_conv_tile_override; initial value from PPN_CONV_TILE="bp,bc"): 0,0 = automatic choice
-static int g_ov_bp = -1, g_ov_bc = 0;
-
-static bool tile_shape_ok(int bp, int bc) {
-    if (bp == 144) return bc == 256;                     // the 8 x 1 wave grid exists for the 256-channel tile only
-    return (bp == 128 || bp == 192 || bp == 256) && (bc == 64 || bc == 128 || bc == 256) && !(bc == 64 && bp == 192);
-}
-
-// relative efficiency of the 144 x 256 tile in the cost model below (PPN_EFF144 overrides: 0 takes the tile out).
-// Measured (round 4, same box, in sequence): the five 24 x 24 512 -> 512 layers 106.5 -> 94.9 us (= 0.93 on this scale), but
-// layer5's 256 -> 256 launches 101.5 -> 118 / 87.8 -> 96.1 us against 192 x 128 at three rounds (= 0.82-0.87): 0.90 picks it
-// for the former only.  It shortens a LONE launch by filling all 256 CUs with smaller, less efficient workgroups (CU-time
-// per launch +19 %): with three lanes in flight the same switch cost 3.5 % of the images/s (10.69 k vs 11.07 k, two
-// interleaved pairs of runs), so plans that share the GPU (PPN_CONV_SHARED_GPU) never take it.
-static const double kEff144 = getenv("PPN_EFF144") ? atof(getenv("PPN_EFF144")) : 0.90;
-
-bool big_tile_for(int cout, long long m, BigTile* out, int ksteps, bool shared_gpu) {
-    if (cout < 64) return false;
-    if (g_ov_bp < 0) {                                   // first call: the environment knob
-        g_ov_bp = g_ov_bc = 0;
-        int bp = 0, bc = 0;
-        const char* ov = getenv("PPN_CONV_TILE");
-        if (ov && sscanf(ov, "%d,%d", &bp, &bc) == 2 && tile_shape_ok(bp, bc)) { g_ov_bp = bp; g_ov_bc = bc; }
-    }
-    // a forced tile applies to every layer whose padded Cout it divides (the packed weights are padded to the
-    // LARGEST channel tile of the layer's Cout class, ppn_conv_tiling, so any smaller power-of-two tile fits)
-    if (g_ov_bp > 0 && g_ov_bc <= ((cout + 63) / 64) * 64 && g_ov_bc <= (cout >= 256 ? 256 : (cout >= 128 ? 128 : 64))) {
-        out->bp = g_ov_bp; out->bc = g_ov_bc;
-        return true;
-    }
-    if (cout >= 4096) {
-        // the head conv (512 -> 7605, K = 512) writes 17.5 MB/image and is store-bound: a 192x128 tile keeps
-        // two workgroups per CU so one's epilogue stores overlap the other's main loop (measured 322 vs 399 us)
-        out->bp = 192; out->bc = 128;
-        return true;
-    }
-    // time ~ ceil(tiles / 256 CUs) * tile area / eff(tile); eff = relative throughput of a tile shape measured on
-    // the 48x48x512 3x3 layers at batch 32 (tools/bench_conv.py with PPN_CONV_TILE), i.e. how well its FLOPs per
-    // staged byte feed the MFMA pipe.  For Cout = 256 the 128-channel tile wins through quantisation
-    // (768 workgroups = 3 full rounds instead of 384 = 1.5).
-    struct Cand { int bp, bc; double eff; };
-    // 144 x 256 (round 4; 8 waves side by side along the channels, each 32 channels x all 144 pixels): 18 432 pixels x 512
-    // channels (the five 24 x 24 layers of DRN-D-22 at batch 32) = exactly 256 workgroups = one full round, where 192 x 256
-    // leaves 64 of the 256 CUs idle; and 73 728 x 256 (layer5) = 512 = two rounds.  Same K order: results unchanged.
-    // (round 4, measured and removed: a 288 x 256 tile -- 4 x 2 wave grid, 36 MFMA tiles per wave, 256 VGPRs with 6 spilled --
-    // makes layer5's 73 728 x 256 launches ONE round of 256 workgroups: 93.9 -> 77.8 us alone, but -1.7 % images/s with three
-    // lanes (a 136 KB workgroup holds its CU alone for 78 us; two 80 KB workgroups of 192 x 128 share one), nothing on a
-    // single lane or the training step, and on the 512-channel layers its two rounds take what 192 x 256's three do.)
-    static const Cand cands[] = {{256, 256, 1.27}, {192, 256, 1.10}, {144, 256, kEff144}, {128, 256, 0.92}, {256, 128, 0.90},
-                                 {192, 128, 0.95}, {128, 128, 0.87}, {256, 64, 0.60},  {128, 64, 0.55}};
-    int bc_max = cout >= 256 ? 256 : (cout >= 128 ? 128 : 64);
-    const int bc_min = cout >= 256 ? 128 : bc_max;
-    // 1x1 projections (<= 8 K steps) are prologue/epilogue-bound: the 128-channel tile's shorter epilogue wins over the
-    // 256-channel tile's staging efficiency (tools/ab_tiles.py: 256->512 at 48x48 32.5 vs 38.4 us, 512->512 stride 2
-    // 15.9 vs 17.1, 128->512 at 24x24 10.7 vs 11.6)
-    if (ksteps > 0 && ksteps <= 8 && bc_max == 256) bc_max = 128;
-    double best = 1e30;
-    for (const Cand& cd : cands) {
-        if (cd.bc > bc_max || cd.bc < bc_min || cd.eff <= 0.0 || (shared_gpu && cd.bp == 144)) continue;
-        const long long tiles = ((m + cd.bp - 1) / cd.bp) * ((cout + cd.bc - 1) / cd.bc);
-        // policy 1 (several launches in flight on different streams, ppn_set_conv_tile_policy): another stream's
-        // workgroups fill a partial last round, so only the tile's efficiency counts
-        // (round 4, measured and dropped: under PPN_CONV_SHARED_GPU, launches with fewer tiles than CUs -- the 24 x 24 layers --
-        // priced by efficiency alone, i.e. 256 x 256 tiles on 144 of the CUs: 10.79 / 10.79 k images/s against 10.83 / 10.84 k
-        // with the whole-round rule, interleaved runs on one box, and 3.25 vs 3.16 ms for the conv stack in sequence)
-        // PPN_POLICY1_MASK (experiment knob, with policy 1): bit 0 = 512-wide layers at >= 65 536 pixels, bit 1 = 512-wide below that,
-        // bit 2 = the narrower layers: which classes are priced by fractional rounds
-        static const int p1mask = getenv("PPN_POLICY1_MASK") ? atoi(getenv("PPN_POLICY1_MASK")) : 7;
-        const int cls = cout >= 512 ? (m >= 65536 ? 1 : 2) : 4;
-        const bool frac = g_tile_policy == 1 && (p1mask & cls);
-        const double rounds = frac ? (double)tiles / 256.0 : (double)((tiles + 255) / 256);
-        const double cost = rounds * cd.bp * cd.bc / cd.eff;
-        if (cost < best) { best = cost; out->bp = cd.bp; out->bc = cd.bc; }
-    }
-    return true;
-}
-
-// Two-segment launch (tile policy 2, opt-in): the most efficient tile (256x256: 1.27 vs 1.10 for 192x256) wastes most
-// of a round when its workgroup count is not a multiple of the 256 CUs (73 728 pixels x 512 channels = 576 tiles =
-// 2.25 rounds), which is why the single-tile choice settles for 192x256 there (768 = 3 rounds).  Cutting the pixel
-// range instead -- whole rounds of the big tile, then ONE round of a small tile over the remaining pixels -- should cost
-// 2 x 51.6 k + 18.8 k = 122 k units instead of 134 k.  MEASURED (round 2, tools/ab_split.sh): the 256x256 segments do
-// run at 1.28-1.46 PFLOP/s (0.51-0.58 of peak) instead of 1.14-1.28, but the lone 128x128 round takes 55-58 us instead of
-// the ~35 the model assumes (one small workgroup per CU stages 2x the bytes per FLOP of the big tile through the same
-// L2->LDS path; a four-stage pipeline changed nothing), so the layer is not faster (277 us either way) and the extra
-// launches cost 1.8 % (three lanes) to 3.6 % (one lane) of throughput.  Not the default; kept for the pixel-range
-// interface it exercises.  Returns the cut (0: single launch).  Only for Cout >= 256, where efficiencies were measured.
-long long big_split_for(int cout, long long m) {
-    BigTile single;
-    if (g_tile_policy != 2 || cout < 256 || cout >= 4096 || !big_tile_for(cout, m, &single) || g_ov_bp > 0) return 0;
-    struct Cand { int bp, bc; double eff; };
-    static const Cand cands[] = {{256, 256, 1.27}, {192, 256, 1.10}, {128, 256, 0.92}, {256, 128, 0.90},
-                                 {192, 128, 0.95}, {128, 128, 0.87}};
-    auto rounds_cost = [&](const Cand& cd, long long mm) {
-        const long long tiles = ((mm + cd.bp - 1) / cd.bp) * ((cout + cd.bc - 1) / cd.bc);
-        return (double)((tiles + 255) / 256) * cd.bp * cd.bc / cd.eff;
-    };
-    double best_single = 1e30;
-    for (const Cand& cd : cands) best_single = std::min(best_single, rounds_cost(cd, m));
-    double best = best_single * 0.96;                    // the second launch must pay for its own start-up
-    long long cut = 0;
-    for (const Cand& p : cands) {
-        const long long ct = (cout + p.bc - 1) / p.bc;
-        if (256 % ct != 0) continue;
-        const long long rounds = (m / p.bp) * ct / 256;  // whole rounds of whole tiles
-        if (rounds < 1) continue;
-        const long long m1 = rounds * 256 / ct * p.bp;
-        if (m1 >= m) continue;
-        double tail = 1e30;
-        for (const Cand& q : cands) tail = std::min(tail, rounds_cost(q, m - m1));
-        const double cost = (double)rounds * p.bp * p.bc / p.eff + tail;
-        if (cost < best) { best = cost; cut = m1; }
-    }
-    return cut;
-}
-
-// Does a launch of this tile carry the BatchNorm-statistics epilogue (ppn_conv_desc.stats_mode)?  The caller (conv_launch) adds
-// the per-launch conditions of the single-output 16-bit epilogue.
-bool big_stats_ok(int dtype, BigTile t) {
-    return dtype == PPN_BF16 && conv_waves() == 8 && stats_tile_ok(t.bp, t.bc);
-}
-
-// Strip loader (kernel flag SP): on (1) / off (0) for every later launch and plan run; -1 = not yet read from PPN_CONV_STRIP
-static int g_strip_on = -1;
-thread_local int g_last_strip = 0;
-
-// Does this launch take the strip loader?  3x3, stride 1, "same" padding on the 192 x 256 tile of a 16-bit mode, plain
-// NHWC epilogues, and every tile R = 192 / Wo whole rows of one image; the strip of R rows at pitch P = Wo + margins
-// (P = Wo (mod 8), room for 2 * dil columns of padding) must fit the 256-row buffer.
-static bool strip_eligible(const ConvKArgs& a, int dtype, BigTile t, int* rows, int* pitch) {
-    if (g_strip_on < 0) g_strip_on = (getenv("PPN_CONV_STRIP") && atoi(getenv("PPN_CONV_STRIP")) == 0) ? 0 : 1;
-    if (!g_strip_on || conv_waves() != 8 || t.bp != 192 || t.bc != 256 || (dtype != PPN_BF16 && dtype != PPN_F16)) return false;
-    if (a.ks != 3 || a.stride != 1 || a.dil < 1 || a.pad != a.dil || a.Ho != a.H || a.Wo != a.W || a.Ktot != 9 * a.Cin) return false;
-    if (a.src2 || a.st_mode != 0 || a.nchw || a.amax_keys || a.unary_out) return false;
-    if (192 % a.Wo != 0 || a.HoWo % 192 != 0 || a.m_base % 192 != 0 || (a.M - a.m_base) % 192 != 0) return false;
-    const int r = 192 / a.Wo, p = a.Wo + 8 * ((2 * a.dil + 7) / 8);
-    if (r * p > 256) return false;
-    *rows = r; *pitch = p;
-    return true;
-}
-
-int launch_big(const ConvKArgs& a, int dtype, BigTile t, hipStream_t st, const char** kname) {
-    // buffer descriptors address up to 2 GiB with the out-of-range marker used for padding
-    const size_t es = dtype == PPN_F32 ? 4 : 2;
-    if ((size_t)a.B * a.H * a.W * a.Cin * es >= 0x7fffff00ull || (size_t)a.n_ctiles * t.bc * a.Ktot * es >= 0x7fffff00ull)
-        return ppn::fail(PPN_E_UNSUPPORTED, "tensor too large for the buffer-addressed conv kernel");
-    if (dtype == PPN_F32) return launch_T<float>(a, t, st, kname);
-    if (dtype == PPN_F16X3) return launch_X3(a, t, st, kname);
-    ConvKArgs b = a;
-    b.sp_rows = b.sp_pitch = 0;
-    b.sp_div = make_fastdiv(1);
-    if (strip_eligible(a, dtype, t, &b.sp_rows, &b.sp_pitch)) b.sp_div = make_fastdiv((unsigned)b.sp_pitch);
-    const int rc = dtype == PPN_F16 ? launch_T<_Float16>(b, t, st, kname) : launch_T<__bf16>(b, t, st, kname);
-    if (rc == PPN_OK) g_last_strip = b.sp_rows > 0 ? 1 : 0;
-    return rc;
-}
-
-}  // namespace ppnconv
-
-extern "C" int ppn_set_conv_tile_override(int32_t bp, int32_t bc) {
-    if (bp == 0 && bc == 0) { ppnconv::g_ov_bp = ppnconv::g_ov_bc = 0; return PPN_OK; }
-    if (!ppnconv::tile_shape_ok(bp, bc))
-        return ppn::fail(PPN_E_INVALID, "ppn_set_conv_tile_override: bp in {128,192,256}, bc in {64,128,256}, not 192x64; or 144x256");
-    ppnconv::g_ov_bp = bp; ppnconv::g_ov_bc = bc;
-    return PPN_OK;
-}
-
-extern "C" int ppn_set_conv_strip_enabled(int32_t on) {
-    ppnconv::g_strip_on = on ? 1 : 0;
-    return PPN_OK;
-}
-
-extern "C" int ppn_set_conv_tile_policy(int32_t policy) {
-    if (policy < 0 || policy > 2) return ppn::fail(PPN_E_INVALID, "ppn_set_conv_tile_policy: 0, 1 or 2");
-    ppnconv::g_tile_policy = policy;
-    return PPN_OK;
+int ppnconv::launch_big(const ConvSegment& s, hipStream_t st) {
+    if (s.x3) return launch_X3(s, st);
+    if (s.dtype == PPN_F32) return launch_T<float>(s, st);
+    return s.dtype == PPN_F16 ? launch_T<_Float16>(s, st) : launch_T<__bf16>(s, st);
 }

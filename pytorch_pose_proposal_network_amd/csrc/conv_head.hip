@@ -23,6 +23,7 @@
 #include <utility>
 
 #include "conv_common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -422,11 +423,8 @@ __global__ void __launch_bounds__(64 * NW, 2) head_limb_argmax_kernel(HeadArgs a
 }
 
 template <typename T>
-int launch_T(const HeadArgs& a, int batch, hipStream_t st, const char** kname) {
+int launch_T(const HeadArgs& a, hipStream_t st) {
     constexpr size_t lds = 2 * (size_t)STAGE + SCRATCH;
-    static char name[80];
-    if (!name[0]) snprintf(name, sizeof(name), "head_limb_argmax_kernel<%s>", elem_name<T>());
-    if (kname) *kname = name;
     auto k = head_limb_argmax_kernel<T>;
     {
         static int max_lds_set = 0;
@@ -447,7 +445,6 @@ int launch_T(const HeadArgs& a, int batch, hipStream_t st, const char** kname) {
     const size_t wgt_bytes = (size_t)a.n_edges * BC * a.Ktot * sizeof(T);
     hipLaunchKernelGGL(k, dim3(grid), dim3(64 * NW), lds, st, a, (unsigned)src_bytes, (unsigned)wgt_bytes);
     PPN_LAUNCH_CHECK();
-    (void)batch;
     return PPN_OK;
 }
 
@@ -455,17 +452,9 @@ int launch_T(const HeadArgs& a, int batch, hipStream_t st, const char** kname) {
 
 namespace ppn {
 
-// called by conv_launch (conv.hip) for descriptors with limb_edge_pad != 0, after validation
-int head_limb_launch(const ppn_conv_desc* d, long long m_lo, long long m_hi, hipStream_t st, const char** kname) {
-    if (d->ksize != 1 || d->stride != 1 || d->pad != 0 || d->scale1)
-        return ppn::fail(PPN_E_UNSUPPORTED, "limb_edge_pad: the head conv is 1x1, stride 1, no padding, bias only (scale1 NULL)");
-    const int bk = d->dtype == PPN_F32 ? 32 : 64;
-    if (d->k_total % (2 * bk) != 0)
-        return ppn::fail(PPN_E_UNSUPPORTED, "limb_edge_pad: k_total must be a multiple of %d (an even number of K steps)", 2 * bk);
-    const size_t es = d->dtype == PPN_F32 ? 4 : 2;
-    const long long m_all = (long long)d->batch * d->out_h * d->out_w;
-    if ((size_t)m_all * d->cin * es >= 0x7fffff00ull || (size_t)d->cout_pad * d->k_total * es >= 0x7fffff00ull)
-        return ppn::fail(PPN_E_UNSUPPORTED, "tensor too large for the buffer-addressed head kernel");
+// descriptors with limb_edge_pad != 0; validated and cut into its pixel range by conv_route.cpp
+int head_limb_launch(const ppn_conv_desc* d, const ppnconv::ConvSegment& s, hipStream_t st) {
+    const long long m_lo = s.m_lo, m_hi = s.m_hi;
     HeadArgs a;
     a.src = static_cast<const char*>(d->src);
     a.wgt = static_cast<const char*>(d->weight);
@@ -486,9 +475,9 @@ int head_limb_launch(const ppn_conv_desc* d, long long m_lo, long long m_hi, hip
     a.dbg = nullptr;
 #endif
     // M is the END of the range in the whole tensor; the source descriptor must cover every row below it
-    if (d->dtype == PPN_F32) return launch_T<float>(a, d->batch, st, kname);
-    if (d->dtype == PPN_F16) return launch_T<_Float16>(a, d->batch, st, kname);
-    return launch_T<__bf16>(a, d->batch, st, kname);
+    if (d->dtype == PPN_F32) return launch_T<float>(a, st);
+    if (d->dtype == PPN_F16) return launch_T<_Float16>(a, st);
+    return launch_T<__bf16>(a, st);
 }
 
 }  // namespace ppn

@@ -17,7 +17,7 @@
 // workgroup and summed in one order, so a result depends neither on the grid nor on what runs beside it; image i of a batch
 // gets bit for bit what it gets alone.
 #include "conv_common.h"
-#include "splitk_partition.h"
+#include "launchers.h"
 
 namespace {
 
@@ -229,52 +229,10 @@ __global__ void __launch_bounds__(256) conv_splitk_reduce_kernel(ConvKArgs a, Sp
     }
 }
 
-// Scope of the split-K path and the partition of a descriptor.  Pointers are not looked at.
-int splitk_check(const ppn_conv_desc* d, Partition* part) {
-    if (!d) return ppn::fail(PPN_E_INVALID, "conv desc is NULL");
-    if (d->dtype != PPN_F32 && d->dtype != PPN_BF16 && d->dtype != PPN_F16 && d->dtype != PPN_F16X3)
-        return ppn::fail(PPN_E_INVALID, "bad dtype %d", d->dtype);
-    if (d->dtype == PPN_F16X3) return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_SPLIT_K: no PPN_F16X3 form");
-    if (d->src2) return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_SPLIT_K: no fused projection shortcut (src2)");
-    if (d->out_nchw_f32 || d->argmax_keys || d->unary_out || d->limb_edge_pad)
-        return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_SPLIT_K: NHWC outputs only (no NCHW head, arg-max or edge-tile mode)");
-    if (d->stats_mode != 0) return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_SPLIT_K: no BatchNorm statistics (stats_mode)");
-    if (d->flags & PPN_CONV_X3_PLAIN_OUT) return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_SPLIT_K: no PPN_CONV_X3_PLAIN_OUT");
-    if ((d->flags & PPN_CONV_OUT_BF16) && d->dtype != PPN_F16)
-        return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_OUT_BF16: a PPN_F16 launch");
-    if (d->batch < 1 || d->in_h < 1 || d->in_w < 1 || d->cin < 1 || d->cout < 1 || d->stride < 1 || d->dilation < 1 || d->pad < 0)
-        return ppn::fail(PPN_E_INVALID, "bad conv geometry");
-    if (d->ksize != 1 && d->ksize != 3) return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_SPLIT_K: ksize 1 or 3 (got %d)", d->ksize);
-    const int bk = d->dtype == PPN_F32 ? 32 : 64;
-    if (d->cin % bk != 0) return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_SPLIT_K: cin %d must be a multiple of the K step %d", d->cin, bk);
-    if (d->m_count != 0) return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_SPLIT_K: whole-tensor launches only (m_count = 0)");
-    if (d->act1 < PPN_ACT_NONE || d->act1 > PPN_ACT_LRELU || d->act2 < PPN_ACT_NONE || d->act2 > PPN_ACT_LRELU)
-        return ppn::fail(PPN_E_UNSUPPORTED, "sigmoid is only implemented for the NCHW head output");
-    if (d->cout % 8 != 0) return ppn::fail(PPN_E_UNSUPPORTED, "NHWC output needs cout %% 8 == 0 (got %d)", d->cout);
-    if (d->cout_pad < d->cout || d->cout_pad % kTileC != 0)
-        return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_SPLIT_K: cout_pad %d must be a multiple of %d and >= cout", d->cout_pad, kTileC);
-    const int eff = d->dilation * (d->ksize - 1) + 1;
-    const int oh = (d->in_h + 2 * d->pad - eff) / d->stride + 1, ow = (d->in_w + 2 * d->pad - eff) / d->stride + 1;
-    if (oh != d->out_h || ow != d->out_w || oh < 1 || ow < 1)
-        return ppn::fail(PPN_E_INVALID, "out size %dx%d inconsistent with %dx%d", d->out_h, d->out_w, oh, ow);
-    const long long kreal = (long long)d->ksize * d->ksize * d->cin;
-    if (d->k_total != kreal) return ppn::fail(PPN_E_INVALID, "k_total %d != %lld", d->k_total, kreal);
-    const long long m = (long long)d->batch * d->out_h * d->out_w;
-    const long long in_elems = (long long)d->batch * d->in_h * d->in_w * d->cin;
-    if (m > 0x7fffffffLL || in_elems > 0x7fffffffLL || m * d->cout > 0x7fffffffLL * 8)
-        return ppn::fail(PPN_E_UNSUPPORTED, "tensor too large for 32-bit indexing");
-    if (!partition(d->dtype == PPN_F32, d->k_total, m, d->cout_pad, part))
-        return ppn::fail(PPN_E_INVALID, "PPN_CONV_SPLIT_K: the GEMM depth cannot be partitioned");
-    return PPN_OK;
-}
-
 template <typename T>
-int launch_partial(const ConvKArgs& a, const SplitKArgs& k, hipStream_t st, const char** kname) {
+int launch_partial(const ConvKArgs& a, const SplitKArgs& k, hipStream_t st) {
     constexpr int BP = kTileP, BC = kTileC;
     auto fn = conv_splitk_partial_kernel<T, BP, BC, 2, 2>;
-    static char name[96];
-    if (!name[0]) snprintf(name, sizeof(name), "conv_splitk_partial_kernel<%s, %d, %d, 2, 2>", elem_name<T>(), BP, BC);
-    if (kname) *kname = name;
     constexpr int lds = 2 * (BP + BC) * 128;
     static int max_lds_set = 0;
     PPN_LDS_ONCE(max_lds_set, reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -293,58 +251,21 @@ int launch_reduce(const ConvKArgs& a, const SplitKArgs& k, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int ppn_conv_splitk_workspace(const ppn_conv_desc* d, int64_t* bytes, int32_t* slabs) {
-    Partition p;
-    if (const int rc = splitk_check(d, &p)) return rc;
-    if (bytes) *bytes = p.ws_bytes;
-    if (slabs) *slabs = p.slabs;
-    return PPN_OK;
-}
-
-namespace ppn {
-int splitk_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname) {
-    Partition p;
-    if (const int rc = splitk_check(d, &p)) return rc;
-    if (!d->src || !d->weight || !d->zero_page) return ppn::fail(PPN_E_INVALID, "NULL src/weight/zero_page");
-    if (!d->out_raw && !d->out_act) return ppn::fail(PPN_E_INVALID, "conv has no output");
-    if (!d->splitk_ws || d->splitk_ws_bytes < p.ws_bytes)
-        return ppn::fail(PPN_E_INVALID, "PPN_CONV_SPLIT_K: splitk_ws is NULL or holds %lld of the %lld bytes "
-                                        "ppn_conv_splitk_workspace asks for", (long long)d->splitk_ws_bytes, p.ws_bytes);
-    if ((reinterpret_cast<size_t>(d->splitk_ws) & 15) != 0)
-        return ppn::fail(PPN_E_INVALID, "PPN_CONV_SPLIT_K: splitk_ws must be 16-byte aligned");
-    ConvKArgs a{};
-    a.src = static_cast<const char*>(d->src);
-    a.wgt = static_cast<const char*>(d->weight);
-    a.scale1 = d->scale1; a.shift1 = d->shift1;
-    a.residual = static_cast<const char*>(d->residual);
-    a.out_raw = static_cast<char*>(d->out_raw);
-    a.scale2 = d->scale2; a.shift2 = d->shift2;
-    a.out_act = static_cast<char*>(d->out_act);
-    a.zero = static_cast<const char*>(d->zero_page);
-    a.B = d->batch; a.H = d->in_h; a.W = d->in_w; a.Cin = d->cin; a.Ho = d->out_h; a.Wo = d->out_w; a.Cout = d->cout;
-    a.ks = d->ksize; a.stride = d->stride; a.dil = d->dilation; a.pad = d->pad;
-    a.Ktot = d->k_total; a.M = (int)p.m; a.m_base = 0; a.HoWo = d->out_h * d->out_w;
-    a.div_howo = make_fastdiv((unsigned)a.HoWo); a.div_wo = make_fastdiv((unsigned)d->out_w);
-    a.act1 = d->act1; a.act2 = d->act2; a.nchw = 0;
-    a.n_ctiles = d->cout_pad / kTileC;
-    a.div_nct = make_fastdiv((unsigned)a.n_ctiles);
-    a.n_ptiles = (int)((p.m + kTileP - 1) / kTileP);
-    a.out_bf16 = (d->flags & PPN_CONV_OUT_BF16) ? 1 : 0;
-    if ((long long)a.n_ctiles * a.n_ptiles > 0x7fffffffLL || p.slabs > 65535)
-        return ppn::fail(PPN_E_UNSUPPORTED, "PPN_CONV_SPLIT_K: grid too large");
+// the segment's scope checks, partition and kernel arguments come from conv_route.cpp
+int ppn::splitk_launch(const ppn_conv_desc* d, const ConvSegment& s, hipStream_t st) {
+    const ConvKArgs& a = s.args;
     SplitKArgs k;
     k.ws = static_cast<float*>(d->splitk_ws);
     k.cout_pad = d->cout_pad;
-    k.steps_per_slab = p.steps_per_slab;
+    k.steps_per_slab = s.splitk.steps_per_slab;
     k.korder1 = d->cout >= 64 ? 1 : 0;             // ppn_conv_tiling: the large-tile layers' packs are channel-chunk-major
-    k.slabs = p.slabs;
+    k.slabs = s.splitk.slabs;
     int rc;
-    if (d->dtype == PPN_F32) rc = launch_partial<float>(a, k, st, kname);
-    else if (d->dtype == PPN_F16) rc = launch_partial<_Float16>(a, k, st, kname);
-    else rc = launch_partial<__bf16>(a, k, st, kname);
+    if (d->dtype == PPN_F32) rc = launch_partial<float>(a, k, st);
+    else if (d->dtype == PPN_F16) rc = launch_partial<_Float16>(a, k, st);
+    else rc = launch_partial<__bf16>(a, k, st);
     if (rc != PPN_OK) return rc;
     if (d->dtype == PPN_F32) return launch_reduce<float, false>(a, k, st);
     if (d->dtype == PPN_BF16) return launch_reduce<__bf16, false>(a, k, st);
     return a.out_bf16 ? launch_reduce<_Float16, true>(a, k, st) : launch_reduce<_Float16, false>(a, k, st);
 }
-}  // namespace ppn

@@ -4,23 +4,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
-
-namespace ppn {
-int conv_launch(const ppn_conv_desc* d, hipStream_t st, const char** kname);
-int split_x3_launch(const float* src, long long pixels, int channels, void* dst, hipStream_t st);
-int block64_launch(const ppn_block_desc* d, hipStream_t st, const char** kname);
-int stem_launch(int dtype, int src_is_u8, const void* src, int batch, int h, int w, const float* weight,
-                const float* scale, const float* shift, const float* mean, const float* stdv, void* out,
-                hipStream_t st);
-int stem01_launch(int dtype, int src_is_u8, const void* src, int batch, int h, int w, const float* w0,
-                  const float* s0, const float* b0, const float* mean, const float* stdv, const float* w1,
-                  const float* s1, const float* b1, void* out, hipStream_t st);
-int stem012_launch(int dtype, int src_is_u8, const void* src, int batch, int h, int w, const float* w0, const float* s0,
-                   const float* b0, const float* mean, const float* stdv, const float* w1, const float* s1,
-                   const float* b1, const float* w2, const float* s2, const float* b2, const float* s3, const float* b3,
-                   void* out_raw, void* out_act, hipStream_t st);
-}  // namespace ppn
+#include "launchers.h"
 
 struct ppn_plan {
     struct Op {

@@ -44,7 +44,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "launchers.h"
 
 // timing-only diagnostics (results wrong): -DPPN_S012_SKIP=mask, 1 convert, 2 layer0, 4 layer1, 8 layer2, 16 requests, 32 layer-2 epilogue
 #ifndef PPN_S012_SKIP
@@ -603,10 +603,6 @@ __global__ void __launch_bounds__(256, 2) stem012_kernel(Stem012Args a) {
 }  // namespace
 
 namespace ppn {
-int stem012_x3_launch(int src_is_u8, const void* src, int batch, int h, int w, const float* w0, const float* s0,
-                      const float* b0, const float* mean, const float* stdv, const float* w1, const float* s1,
-                      const float* b1, const float* w2, const float* s2, const float* b2, const float* s3, const float* b3,
-                      void* out_raw, void* out_act, hipStream_t st);
 
 template <bool U8, typename H, typename HO = H>
 static int stem012_launch_T(const Stem012Args& a, unsigned grid, hipStream_t st) {

@@ -11,7 +11,7 @@
 // pre-activation of the first BasicBlock (drn.py:45-46).
 #include <hip/hip_bf16.h>
 
-#include "common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -212,29 +212,18 @@ int launch(const Stem3Args& a, hipStream_t st) {
 
 }  // namespace
 
-namespace ppn {
-// 3x3, pad 1, Cin 16, Cout in {16,32}, stride in {1,2}; weight in the reference layout (f32, device).
-bool stem3x3_supported(int cin, int cout, int ksize, int stride, int dilation, int pad) {
-    return cin == 16 && (cout == 16 || cout == 32) && ksize == 3 && (stride == 1 || stride == 2) && dilation == 1 &&
-           pad == 1;
-}
-
-int stem3x3_launch(int dtype, const void* src, int batch, int h, int w, int cout, int stride, const float* weight,
-                   const float* scale1, const float* shift1, const float* scale2, const float* shift2, void* out_raw,
-                   void* out_act, hipStream_t st, const char** kname) {
-    if (!src || !weight || (scale1 == nullptr) != (shift1 == nullptr) || (!out_raw && !out_act) || batch < 1 ||
-        h < 1 || w < 1)
-        return fail(PPN_E_INVALID, "stem3x3: bad arguments");
+// The scope (3x3, pad 1, Cin 16, Cout in {16,32}, stride in {1,2}; weight in the reference layout, f32, device) and the
+// descriptor checks are conv_route.cpp's.
+int ppn::stem3x3_launch(const ppn_conv_desc* d, hipStream_t st) {
     Stem3Args a;
-    a.src = src; a.weight = weight; a.scale1 = scale1; a.shift1 = shift1; a.scale2 = scale2; a.shift2 = shift2;
-    a.out_raw = out_raw; a.out_act = out_act;
-    a.B = batch; a.H = h; a.W = w;
-    a.Ho = (h + 2 - 3) / stride + 1; a.Wo = (w + 2 - 3) / stride + 1;
+    a.src = d->src; a.weight = static_cast<const float*>(d->weight);
+    a.scale1 = d->scale1; a.shift1 = d->shift1; a.scale2 = d->scale2; a.shift2 = d->shift2;
+    a.out_raw = d->out_raw; a.out_act = d->out_act;
+    a.B = d->batch; a.H = d->in_h; a.W = d->in_w;
+    a.Ho = d->out_h; a.Wo = d->out_w;
     a.tiles_x = a.tiles_y = 0;                            // per instantiation: launch<>()
-    static char name[64];
-    snprintf(name, sizeof(name), "stem3x3_kernel<%s, %d, %d>", dtype == PPN_F32 ? "float" : "__bf16", cout, stride);
-    if (kname) *kname = name;
-    if (dtype == PPN_F32) {
+    const int cout = d->cout, stride = d->stride;
+    if (d->dtype == PPN_F32) {
         if (cout == 16 && stride == 1) return launch<float, 16, 1>(a, st);
         if (cout == 32 && stride == 2) return launch<float, 32, 2>(a, st);
         if (cout == 16 && stride == 2) return launch<float, 16, 2>(a, st);
@@ -245,4 +234,3 @@ int stem3x3_launch(int dtype, const void* src, int batch, int h, int w, int cout
     if (cout == 16 && stride == 2) return launch<__bf16, 16, 2>(a, st);
     return launch<__bf16, 32, 1>(a, st);
 }
-}  // namespace ppn

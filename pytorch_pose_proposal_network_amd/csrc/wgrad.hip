@@ -27,12 +27,7 @@
 // Algorithmic work: 2*P*cout*cin*k*k flops; unique bytes: x + dy once each.
 #include "common.h"
 #include "conv_common.h"
-
-namespace ppn {   // stem_wgrad.hip: dedicated kernel for the small-channel stem layers (bf16)
-bool stem_wgrad_supported(const ppn_wgrad_desc* d);
-size_t stem_wgrad_workspace_bytes(const ppn_wgrad_desc* d);
-int stem_wgrad_launch(const ppn_wgrad_desc* d, hipStream_t st);
-}  // namespace ppn
+#include "launchers.h"   // stem_wgrad.hip: dedicated kernel for the small-channel stem layers (bf16)
 
 namespace {
 
