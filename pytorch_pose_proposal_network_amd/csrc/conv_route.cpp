@@ -323,6 +323,9 @@ int route_segment(const ppn_conv_desc* d, const RouteKnobs& k, ConvSegment* s, l
         ((d->act1 == PPN_ACT_RELU && d->scale1 && d->shift1) ||
          (d->act1 == PPN_ACT_NONE && !d->scale1 && !d->shift1 && !d->out_act)) &&
         (!d->out_act || d->act2 == PPN_ACT_RELU)) {
+        // stem3x3.hip is instantiated for float and __bf16: an IEEE-half tensor would be read as bf16 bits
+        if (d->dtype != PPN_F32 && d->dtype != PPN_BF16)
+            return ppn::fail(PPN_E_UNSUPPORTED, "stem3x3 (16 -> 16 / 32 channels, 3x3, pad 1) runs as PPN_F32 or PPN_BF16 only");
         if (!d->src || !d->weight) return ppn::fail(PPN_E_INVALID, "NULL src/weight");
         if ((d->scale1 == nullptr) != (d->shift1 == nullptr) || (!d->out_raw && !d->out_act))
             return ppn::fail(PPN_E_INVALID, "stem3x3: bad arguments");

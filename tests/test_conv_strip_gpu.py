@@ -19,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import forward_cases as FC
 from test_conv_gpu import BF16_TOL, F16_TOL, q, rnd, run_conv
 
 pytestmark = pytest.mark.gpu
@@ -115,6 +116,10 @@ def test_strip_against_torch_cpu_f32(strip, dtype_name, geom):
     err = float((on - ref).abs().max())
     print("max |gpu - cpu f32| = %.3g (tolerance %.3g)" % (err, tol))
     assert not torch.isnan(on).any() and err <= tol
+    # per element against f64 (tests/forward_cases.py): the strip loader has no f32 form to hold it tighter
+    r = FC.ratios_of(dtype_name, x, w, 1, dil, dil, s1, b1, act1=1, raw=on)
+    print("per-element bound: ratio %.3f" % r["raw"])
+    assert r["raw"] <= 1.0
 
 
 def test_ineligible_launches_keep_the_per_tap_loader(strip):

@@ -11,7 +11,8 @@ ppn_last_conv_kernel(), ppn_last_conv_strip(), *stats_tiles and, under tile poli
 
 The expected values are those of the library the recorder runs on, so the fixture is recorded at the commit BEFORE a change of the
 dispatch and replayed after it (tests/test_conv_route_cpu.py, tests/test_conv_route_gpu.py).  The `manual` entries at the end are the
-only ones written by hand: stride < 1, dilation < 1 and pad < 0 are PPN_E_INVALID ("bad conv geometry").
+only ones written by hand: stride < 1, dilation < 1 and pad < 0 are PPN_E_INVALID ("bad conv geometry"); so are the two `rejected`
+entries of the stem3x3 shapes in PPN_F16 / PPN_F16X3, which the library used to run on the bf16 kernel.
 """
 import ctypes as C
 import json
@@ -286,6 +287,9 @@ def negatives(L):
     neg(valid(L, F32, 16, 16, k_total=144, cout_pad=16, act1=L.PPN_ACT_RELU, scale1=P, shift1=P), src=None)     # stem3x3 route
     neg(valid(L, F32, 16, 32, k_total=144, cout_pad=32), weight=None)
     neg(valid(L, F32, 16, 16, k_total=144, cout_pad=16), out_raw=None)                                           # stem3x3_launch
+    # stem3x3.hip has no IEEE-half form (these two entries of the fixture were written by hand when the refusal was added)
+    neg(valid(L, F32, 16, 16, k_total=144, cout_pad=16, act1=L.PPN_ACT_RELU, scale1=P, shift1=P), dtype=F16)
+    neg(valid(L, F32, 16, 32, stride=2, k_total=144, cout_pad=32), dtype=X3)
     neg(valid(L, F32, 8, 24), cin=24, k_total=224)
     neg(valid(L, X3, 64, 128), cout=32)
     neg(valid(L, X3, 64, 128), limb_edge_pad=448)
