@@ -454,12 +454,54 @@ int ppn_ingest_frames(const void* src_bgr, int32_t batch, int32_t src_h, int32_t
  *   A person whose 2 * (K - 1) keypoint values are all 0 is removed; the survivors keep their order (any pmax);
  *   count_out[b] = survivors (0 when nobody is left), rows beyond it are zeroed in people_out and visible_out.
  * The outputs must not alias the inputs.
+ *
+ * Options of the stage (not in aug.py; NumPy restatement tests/augment_jitter_ref.py).  With both off nothing above changes.
+ *
+ * Left-right mirror.  The HOST composes the reflection x -> (w - 1) - x (w = the picture's valid width) into F and F^-1,
+ * applied to the source point before the rotation; the image kernels need nothing else.  The labels additionally swap
+ * their left / right slots:
+ * ppn_augment_people_mirror: every rule of ppn_augment_people, and in an image with mirror[b] != 0 output point slot j
+ *   (keypoint j + 1; keypoint 0, the instance, has no slot) takes input point slot mj = kp_mirror[j + 1] - 1: its
+ *   coordinates, which then go through F, and its visible bit (output bit j = input bit mj, cleared afterwards if the mapped
+ *   point is (0, 0)).  Visible bits K - 1 and above have no slot and are copied.  The head box and `size` are not permuted.
+ *   mirror     i32 [batch] device, or NULL: nobody is mirrored.  NULL or a flag of 0 gives ppn_augment_people's bytes.
+ *   kp_mirror  i32 [K] HOST (tta.mirror_tables()): validated here, an involution on 0..K-1 with kp_mirror[0] == 0, and
+ *              passed to the kernel by value.
+ *   PPN_E_INVALID: a NULL pointer other than mirror, an output that is one of the inputs, K outside 1..PPN_MAX_KP, a
+ *   non-positive size, a table that is not such an involution; nothing is launched then.
+ *
+ * Colour and noise.
+ * ppn_augment_images_color: ppn_augment_images with a colour step between the interpolation and the stores.
+ *   color  i32 [batch][10] device: {sat, gain_r, gain_g, gain_b, off_r, off_g, off_b, noise_q, key_lo, key_hi}; the kernel
+ *          clamps sat to 0..512, gain to 0..1024, off to -255..255 and noise_q to 0..4096 (256 = factor 1).
+ *   (r, g, b) = the three interpolated v of the pixel.  All arithmetic is i32; `>>` on a negative value is an arithmetic
+ *   (floor) shift.
+ *     1. y = (77 r + 150 g + 29 b + 128) >> 8;  per channel c1 = clamp(y + (((c - y) * sat + 128) >> 8), 0, 255)
+ *     2. c2 = ((c1 * gain_c + 128) >> 8) + off_c
+ *     3. idx = oy * out_w + ox;  z = output number idx (0-based) of the splitmix64 stream started at
+ *        key = (u32)key_lo | (u64)(u32)key_hi << 32, i.e. prng.raw_u64(key, out_h * out_w)[idx]: z = key + (idx + 1) *
+ *        0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31
+ *        (u64, wrap-around).  Channel c = 0, 1, 2 (r, g, b): t = (z >> 21 c) & 0x1FFFFF,
+ *        s = 2 * ((t & 127) + ((t >> 7) & 127) + ((t >> 14) & 127)) - 381,  d = (s * noise_q + (1 << 13)) >> 14
+ *        (zero mean, sd = noise_q / 128 in u8 units; the same key gives every image the same field).
+ *     4. c3 = clamp(c2 + d, 0, 255)
+ *   dst_u8 receives c3, dst_f32 ((float)c3 - mean_c) / std_c.  The step applies to EVERY output pixel, the constant-0 border
+ *   included (a partly covered pixel cannot be told from it).  The row (256, 256, 256, 256, 0, 0, 0, 0, *, *) reproduces
+ *   ppn_augment_images bit for bit.  PPN_E_INVALID as ppn_augment_images, and for a NULL color or an output that is one of
+ *   the inputs.
  */
 int ppn_augment_images(const uint8_t* src, const int32_t* src_hw, const float* inv, int32_t batch, int32_t src_h,
                        int32_t src_w, int32_t out_h, int32_t out_w, uint8_t* dst_u8, float* dst_f32, void* stream);
 int ppn_augment_people(const float* people, const int32_t* visible, const int32_t* count, const float* fwd, int32_t batch,
                        int32_t pmax, int32_t K, int32_t out_h, int32_t out_w, float* people_out, int32_t* visible_out,
                        int32_t* count_out, void* stream);
+int ppn_augment_images_color(const uint8_t* src, const int32_t* src_hw, const float* inv, const int32_t* color, int32_t batch,
+                             int32_t src_h, int32_t src_w, int32_t out_h, int32_t out_w, uint8_t* dst_u8, float* dst_f32,
+                             void* stream);
+int ppn_augment_people_mirror(const float* people, const int32_t* visible, const int32_t* count, const float* fwd,
+                              const int32_t* mirror, const int32_t* kp_mirror, int32_t batch, int32_t pmax, int32_t K,
+                              int32_t out_h, int32_t out_w, float* people_out, int32_t* visible_out, int32_t* count_out,
+                              void* stream);
 
 /*
  * Drawing the decoded people on the device (datatest.py:162-232, draw_humans), csrc/render.hip: a tiled rasteriser over

@@ -270,6 +270,9 @@ _SIGNATURES.update({
                                     C.c_int32, C.c_int32, C.c_void_p]),
     "ppn_augment_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 3),
     "ppn_augment_people": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p] * 4),
+    "ppn_augment_images_color": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p] * 3),
+    # kp_mirror is a HOST table (the only pointer here the library itself reads)
+    "ppn_augment_people_mirror": (C.c_int, [C.c_void_p] * 5 + [C.POINTER(C.c_int32)] + [C.c_int32] * 5 + [C.c_void_p] * 4),
     "ppn_draw_workspace_bytes": (C.c_size_t, [C.POINTER(DrawCfg), C.c_int32, C.c_int32]),
     "ppn_draw_humans": (C.c_int, [C.POINTER(DrawCfg), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

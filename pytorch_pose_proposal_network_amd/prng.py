@@ -29,6 +29,21 @@ def stream_seed(base_seed: int, index: int) -> int:
     return int(z[0])
 
 
+def stream_seeds(base_seeds, index: int) -> np.ndarray:
+    """stream_seed(b, index) for every b of `base_seeds`, as uint64 [len(base_seeds)]."""
+    with np.errstate(over="ignore"):
+        z = np.asarray(base_seeds, dtype=np.uint64) * _GOLDEN
+        return _mix(z + np.uint64(index) * np.uint64(0xD1B54A32D192ED03) + np.uint64(1))
+
+
+def uniform01_rows(seeds, n: int) -> np.ndarray:
+    """uniform01(s, n) for every s of `seeds`, as float32 [len(seeds), n]."""
+    with np.errstate(over="ignore"):
+        ctr = np.arange(1, n + 1, dtype=np.uint64)[None, :] * _GOLDEN + np.asarray(seeds, dtype=np.uint64)[:, None]
+        x = _mix(ctr) >> np.uint64(40)
+    return (x.astype(np.float64) * (1.0 / 16777216.0)).astype(np.float32)
+
+
 def raw_u64(seed: int, n: int) -> np.ndarray:
     """n outputs of splitmix64 started at `seed`."""
     with np.errstate(over="ignore"):

@@ -3,8 +3,9 @@
     python tools/bench_augment.py [--out profiles/augment_bench.txt] [--calls 50] [--src-h 480 --src-w 640]
 
 Device events around N calls after a warm-up (every shape warmed; one synchronise at the end of each window).  Writes, per
-batch: us of the whole call, of the image launch, of the label launch and of the target encoder behind them; the bytes the
-image kernel must move (f32 planes written + every valid source byte read once) and their rate as a fraction of the chip's
+batch: us of the whole call, of the image launch, of the label launch and of the target encoder behind them, each launch
+plain and with its option (the colour / noise image launch beside the plain one on the same matrices, the mirror label launch
+beside the plain one) in the same run, alternated window by window, and their ratios; the bytes the image kernel must move (f32 planes written + every valid source byte read once) and their rate as a fraction of the chip's
 ~6.3 TB/s copy ceiling; the share of the training step (`train_shard.ms_per_step` of the newest
 profiles/r*_bench.json).  No threshold: the file is the record.  Needs a GPU; there is no fallback."""
 import argparse
@@ -20,6 +21,15 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 COPY_CEILING = 6.3e12
+
+
+def alternated(fns, calls, warmup, rounds=3):
+    """us per call of each fn: `rounds` windows each, the fns taking turns, the smallest window of each (the box is shared)."""
+    best = [float("inf")] * len(fns)
+    for r in range(rounds):
+        for i, fn in enumerate(fns):
+            best[i] = min(best[i], timed(fn, calls, warmup if r == 0 else 2))
+    return best
 
 
 def timed(fn, calls, warmup):
@@ -74,19 +84,40 @@ def main():
         step[0] += 1
         aug(src, hw, packed, step[0])
 
-    t_call = timed(whole, a.calls, a.warmup)
-    p = aug.params
+    cj = A.ColorJitter()
+    aug_opt = A.TrainAugmenter(insize=(size, size), seed=1, mode="train", mirror_p=0.5, color=cj)
+
+    def whole_opt():
+        step[0] += 1
+        aug_opt(src, hw, packed, step[0])
+
+    t_call, t_call_opt = alternated([whole, whole_opt], a.calls, a.warmup)
+    # the launches alone, plain and with their option on the SAME matrices (those of the options' last step: about half the
+    # images mirrored); colour rows: the sampler's (noise on in nearly every image), and the same rows with noise_q = 0
+    p = aug_opt.params
     inv, fwd = torch.from_numpy(p["inv"]).cuda(), torch.from_numpy(p["fwd"]).cuda()
+    rows = torch.from_numpy(p["color"]).cuda()
+    quiet = p["color"].copy()
+    quiet[:, 7] = 0
+    rows_quiet = torch.from_numpy(quiet).cuda()
+    flags = torch.from_numpy(p["mirror"].astype(np.int32)).cuda()
     x = torch.empty((B, 3, size, size), device="cuda")
     pout = tuple(torch.empty_like(v) for v in packed)
-    t_img = timed(lambda: A.augment_images(src, hwd, inv, (size, size), out_f32=x), a.calls, a.warmup)
-    t_ppl = timed(lambda: A.augment_people(packed, fwd, (size, size), out=pout), a.calls, a.warmup)
+    t_img, t_img_col, t_img_quiet = alternated(
+        [lambda: A.augment_images(src, hwd, inv, (size, size), out_f32=x),
+         lambda: A.augment_images(src, hwd, inv, (size, size), out_f32=x, color=rows),
+         lambda: A.augment_images(src, hwd, inv, (size, size), out_f32=x, color=rows_quiet)], a.calls, a.warmup)
+    t_ppl, t_ppl_mir = alternated([lambda: A.augment_people(packed, fwd, (size, size), out=pout),
+                                   lambda: A.augment_people(packed, fwd, (size, size), out=pout, mirror=flags)],
+                                  a.calls, a.warmup)
     tg = T.encode_targets(pout, (size, size), (size // 16, size // 16))
     t_enc = timed(lambda: T.encode_targets(pout, (size, size), (size // 16, size // 16), out=tg), a.calls, a.warmup)
     # val mode reads every valid source pixel (train mode at s > 1 reads a part, at s < 1 writes mostly border)
     pv = A.sample_params(0, 0, hw, (size, size), "val")
     inv_v = torch.from_numpy(pv["inv"]).cuda()
-    t_img_val = timed(lambda: A.augment_images(src, hwd, inv_v, (size, size), out_f32=x), a.calls, a.warmup)
+    t_img_val, t_img_val_col = alternated(
+        [lambda: A.augment_images(src, hwd, inv_v, (size, size), out_f32=x),
+         lambda: A.augment_images(src, hwd, inv_v, (size, size), out_f32=x, color=rows)], a.calls, a.warmup)
 
     wr = B * 3 * size * size * 4
     rd = int((hw[:, 0].astype(np.int64) * hw[:, 1] * 3).sum())
@@ -94,12 +125,24 @@ def main():
     lines = [
         f"augment bench: batch {B}, sources u8 padded to {Hs}x{Ws} (valid {hw[:, 0].min()}..{hw[:, 0].max()} x "
         f"{hw[:, 1].min()}..{hw[:, 1].max()}), output {size}x{size} f32 NCHW, pmax {a.pmax}, "
-        f"{a.calls} calls after {a.warmup} warm-up, device events, {torch.cuda.get_device_name(0)}",
+        f"windows of {a.calls} calls after a warm-up of {a.warmup}, device events, {torch.cuda.get_device_name(0)}",
+        "ONE run on a shared box.  Plain and optioned launches take turns window by window, three windows each, the smallest "
+        "is reported.  Not profiled: no kernel trace, no counters, no run-to-run spread.",
         f"TrainAugmenter.__call__ (sampler on the host + 2 small uploads + image + label + target-encoder launches): "
         f"{t_call:9.1f} us per batch",
-        f"  ppn_augment_images  (train params of the last step): {t_img:9.1f} us per batch",
-        f"  ppn_augment_images  (val: plain resize)            : {t_img_val:9.1f} us per batch",
-        f"  ppn_augment_people                                  : {t_ppl:9.1f} us per batch",
+        f"TrainAugmenter.__call__ with mirror_p=0.5, color=ColorJitter() (same launches, one larger upload)          : "
+        f"{t_call_opt:9.1f} us per batch  ({t_call_opt / t_call:.2f} x)",
+        f"  ppn_augment_images        (train matrices, {int(p['mirror'].sum())} of {B} mirrored) : {t_img:9.1f} us per batch",
+        f"  ppn_augment_images_color  (same matrices, sampled rows)      : {t_img_col:9.1f} us per batch  "
+        f"(colour / plain = {t_img_col / t_img:.2f})",
+        f"  ppn_augment_images_color  (same, noise_q = 0 in every row)   : {t_img_quiet:9.1f} us per batch  "
+        f"(colour / plain = {t_img_quiet / t_img:.2f})",
+        f"  ppn_augment_images        (val: plain resize)                : {t_img_val:9.1f} us per batch",
+        f"  ppn_augment_images_color  (val matrices, sampled rows)       : {t_img_val_col:9.1f} us per batch  "
+        f"(colour / plain = {t_img_val_col / t_img_val:.2f})",
+        f"  ppn_augment_people                                            : {t_ppl:9.1f} us per batch",
+        f"  ppn_augment_people_mirror (same matrices and flags)          : {t_ppl_mir:9.1f} us per batch  "
+        f"(mirror / plain = {t_ppl_mir / t_ppl:.2f})",
         f"  ppn_encode_targets_c (existing, behind them)        : {t_enc:9.1f} us per batch",
         f"image kernel bytes: {wr / 1e6:.1f} MB written (f32 planes) + <= {rd / 1e6:.1f} MB read (every valid source byte "
         f"once) = {(wr + rd) / 1e6:.1f} MB",
@@ -113,7 +156,9 @@ def main():
     ]
     if ref:
         lines.append(f"share of the training step ({ref[0]} train_shard.ms_per_step = {ref[1]:.3f} ms): whole call "
-                     f"{t_call / (ref[1] * 1e3) * 100:.2f} %, the two new launches {(t_img + t_ppl) / (ref[1] * 1e3) * 100:.2f} %")
+                     f"{t_call / (ref[1] * 1e3) * 100:.2f} %, image + label launches {(t_img + t_ppl) / (ref[1] * 1e3) * 100:.2f} %; "
+                     f"with both options: whole call {t_call_opt / (ref[1] * 1e3) * 100:.2f} %, image + label launches "
+                     f"{(t_img_col + t_ppl_mir) / (ref[1] * 1e3) * 100:.2f} %")
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
