@@ -424,6 +424,56 @@ int ppn_ingest_frames(const void* src_bgr, int32_t batch, int32_t src_h, int32_t
                       int32_t dst_w, int32_t flip, int32_t swap_rb, void* stream);
 
 /*
+ * Raw video frames (csrc/ingest.hip): what a hardware decoder (NV12, pitched), a raw ffmpeg pipe (I420) or a UVC camera
+ * without conversion (YUYV) delivers, straight into dst u8 [batch][dst_h][dst_w][3] in ONE launch -- colour conversion,
+ * resize, optional 180-degree flip and the store.  Every output byte equals converting the whole picture to RGB first and
+ * then applying ppn_ingest_frames' resize rule (oracle/ingest_ref.py, incl. the exact-halving (a + b + c + d + 2) >> 2
+ * path) and the flip; only the 4 taps an output pixel needs are converted, each saturated BEFORE the interpolation.
+ *
+ * Pixel rule: OpenCV's fixed-point cvtColor YUV -> RGB (modules/imgproc/src/color_yuv.simd.hpp; parity unpinned, as the
+ * resize: cv2 is not in this image).  For a pixel's bytes Y, U, V and a set (CY, CVR, CVG, CUG, CUB, yoff), all int32:
+ *     y = max(0, Y - yoff) * CY;  uu = U - 128;  vv = V - 128;  h = 1 << 19
+ *     R = sat8((y + h + CVR * vv) >> 20)
+ *     G = sat8((y + h + CVG * vv + CUG * uu) >> 20)
+ *     B = sat8((y + h + CUB * uu) >> 20)
+ * with an arithmetic shift and sat8 = clamp to 0..255; no term exceeds 6e8 in magnitude.  The sets are round(c * 2^20)
+ * of the usual three-decimal constants (ppn_yuv_coefficients returns them; the first row is OpenCV's ITUR_BT_601_*):
+ *     matrix, range            CY       CVR      CVG      CUG      CUB   yoff
+ *     0 bt601, limited    1220542   1673527  -852492  -409993  2116026     16      (the default)
+ *     1 bt709, limited    1220542   1880097  -558891  -223347  2214593     16
+ *     0 bt601, full       1048576   1470104  -748826  -360853  1858077      0
+ *     1 bt709, full       1048576   1651297  -490864  -196423  1945738      0
+ * Chroma is the nearest sample, as in OpenCV: pixel (y, x) uses chroma sample (y >> 1, x >> 1) in NV12 and I420 and
+ * (y, x >> 1) in YUYV.  Layouts:
+ *     PPN_PIX_NV12  y: the Y plane [src_h][pitch];  u: interleaved U, V bytes [src_h / 2][pitch_c];  v: NULL
+ *     PPN_PIX_I420  y: the Y plane;  u, v: [src_h / 2][pitch_c] planes of src_w / 2 bytes per row (YV12: swap u and v)
+ *     PPN_PIX_YUYV  y: packed Y0 U Y1 V per pixel pair, [src_h][pitch];  u = v = NULL
+ * Planes may have any alignment (the taps are byte loads).  dst is stored as dwords when dst_w % 4 == 0 and dst is 4-byte
+ * aligned, as bytes otherwise (same bytes).  PPN_E_INVALID, before any launch: a NULL d, dst or required plane; an unknown
+ * format or matrix; an odd src_w; an odd src_h in NV12 / I420; pitch or pitch_c below the row's bytes; frame_stride below
+ * a plane's bytes ((rows - 1) * pitch + row bytes); a size below 1; batch or dst_h above 65535; src_h or src_w above 16384.
+ * Runs on `stream`, allocates nothing, does not synchronise.
+ */
+#define PPN_PIX_NV12 0
+#define PPN_PIX_I420 1
+#define PPN_PIX_YUYV 2
+typedef struct ppn_ingest_desc {
+    int32_t format, batch, src_h, src_w;
+    int32_t pitch;         /* bytes per row of the Y plane, or of the packed row for YUYV */
+    int32_t pitch_c;       /* bytes per chroma row (NV12: >= src_w, I420: >= src_w/2; ignored for YUYV) */
+    int64_t frame_stride;  /* bytes from one frame to the next, applied to each plane pointer */
+    const void *y, *u, *v; /* NV12: u = the UV plane, v = NULL; YUYV: y = packed data, u = v = NULL */
+    int32_t matrix;        /* 0 bt601, 1 bt709 */
+    int32_t full_range;
+    void* dst;
+    int32_t dst_h, dst_w;
+    int32_t flip;          /* both axes, as ppn_ingest_frames */
+    int32_t dst_bgr;       /* 0: RGB */
+} ppn_ingest_desc;
+int ppn_ingest_yuv(const ppn_ingest_desc* d, void* stream);
+int ppn_yuv_coefficients(int32_t matrix, int32_t full_range, int32_t out6[6]);   /* host only: the table above */
+
+/*
  * Train-time augmentation on the device (aug.py:13-160: IAA + ToNormalizedTensor), csrc/augment.hip.  Coordinates are pixel
  * indices with pixel centres at integers.  Per image the HOST builds the forward map F (source point -> output point:
  * rotation + isotropic scale about ((w-1)/2, (h-1)/2), minus the crop's (left, top), centre-aligned resize

@@ -18,6 +18,7 @@ PPN_MATCH_JOINTS, PPN_MATCH_MAX_GT, PPN_MATCH_MAX_PEOPLE = 17, 64, 1024     # pp
 PPN_MATCH_FLAG_INDEX, PPN_MATCH_FLAG_GT_COUNT = 1, 2
 PPN_TRACK_SLOTS, PPN_TRACK_MAX_DET = 64, 256                                # ppn_track_update (csrc/track.hip)
 PPN_TRACK_FLAG_DET_OVERFLOW, PPN_TRACK_FLAG_SLOT_OVERFLOW = 1, 2
+PPN_PIX_NV12, PPN_PIX_I420, PPN_PIX_YUYV = 0, 1, 2                         # ppn_ingest_desc.format (csrc/ingest.hip)
 PPN_STEM_RAW_S2 = 1 << 16          # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
 
 
@@ -134,6 +135,14 @@ class TrackCfg(C.Structure):
 class TrackState(C.Structure):
     """ppn_track_state: device pointers."""
     _fields_ = [(n, C.c_void_p) for n in ("id", "miss", "hits", "mask", "root", "xy", "last_id", "flags")]
+
+
+class IngestDesc(C.Structure):
+    """ppn_ingest_desc (csrc/ingest.hip: ppn_ingest_yuv)."""
+    _fields_ = [(n, C.c_int32) for n in ("format", "batch", "src_h", "src_w", "pitch", "pitch_c")] + [
+        ("frame_stride", C.c_int64), ("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p),
+        ("matrix", C.c_int32), ("full_range", C.c_int32), ("dst", C.c_void_p)] + [
+        (n, C.c_int32) for n in ("dst_h", "dst_w", "flip", "dst_bgr")]
 
 
 class PPNError(RuntimeError):
@@ -268,6 +277,8 @@ _SIGNATURES.update({
     "ppn_conv_wgrad": (C.c_int, [C.POINTER(WgradDesc), C.c_void_p]),
     "ppn_ingest_frames": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_void_p]),
+    "ppn_ingest_yuv": (C.c_int, [C.POINTER(IngestDesc), C.c_void_p]),
+    "ppn_yuv_coefficients": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ppn_augment_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 3),
     "ppn_augment_people": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p] * 4),
     "ppn_augment_images_color": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p] * 3),

@@ -78,6 +78,88 @@ def grab_frame(cap, size: int = 384, out: Optional[torch.Tensor] = None):
     return ret, ingest_frames(torch.from_numpy(f).unsqueeze(0).cuda(non_blocking=True), size, out)
 
 
+_PIX_FORMATS = {"nv12": 0, "i420": 1, "yuyv": 2}        # lib.PPN_PIX_*
+_YUV_MATRICES = {"bt601": 0, "bt709": 1}
+
+
+def yuv_frame_layout(fmt: str, src_hw, pitch: Optional[int] = None):
+    """Where the planes of one contiguous raw frame sit: ``(nbytes, pitch, pitch_c, u_offset, v_offset)`` (offsets in
+    bytes from the frame's start, None for a plane the format lacks).  NV12: Y [h][pitch], then interleaved UV
+    [h/2][pitch]; I420: Y [h][pitch], U and V [h/2][pitch/2]; YUYV: packed [h][pitch].  `pitch` defaults to tight."""
+    if fmt not in _PIX_FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(_PIX_FORMATS)}, not {fmt!r}")
+    h, w = int(src_hw[0]), int(src_hw[1])
+    row = 2 * w if fmt == "yuyv" else w
+    pitch = row if pitch is None else int(pitch)
+    if h < 1 or w < 1 or w % 2 or (fmt != "yuyv" and h % 2):
+        raise ValueError(f"{fmt} frames need an even width" + ("" if fmt == "yuyv" else " and height") + f", not {h}x{w}")
+    if pitch < row:
+        raise ValueError(f"pitch {pitch} is below the {row} bytes of a {fmt} row of width {w}")
+    if fmt == "yuyv":
+        return h * pitch, pitch, 0, None, None
+    if fmt == "nv12":
+        return h * pitch + (h // 2) * pitch, pitch, pitch, h * pitch, None
+    if pitch % 2:
+        raise ValueError("i420 needs an even pitch (the chroma pitch is pitch // 2)")
+    pc = pitch // 2
+    return h * pitch + 2 * (h // 2) * pc, pitch, pc, h * pitch, h * pitch + (h // 2) * pc
+
+
+def _launch_ingest_yuv(raw: torch.Tensor, fmt: str, src_hw, out: torch.Tensor, flip: bool, matrix: str,
+                       full_range: bool, pitch: Optional[int]):
+    """ppn_ingest_yuv on the current stream: `raw` u8 [B,nbytes] on the device (rows of unit stride), `out` u8 [B,h,w,3]."""
+    from . import lib as L
+    if matrix not in _YUV_MATRICES:
+        raise ValueError(f"matrix must be one of {sorted(_YUV_MATRICES)}, not {matrix!r}")
+    nbytes, pitch, pitch_c, u_off, v_off = yuv_frame_layout(fmt, src_hw, pitch)
+    if raw.shape[1] < nbytes:
+        raise ValueError(f"a {fmt} frame of {tuple(src_hw)} with pitch {pitch} has {nbytes} bytes, raw rows have {raw.shape[1]}")
+    base = raw.data_ptr()
+    d = L.IngestDesc(format=_PIX_FORMATS[fmt], batch=raw.shape[0], src_h=int(src_hw[0]), src_w=int(src_hw[1]), pitch=pitch,
+                     pitch_c=pitch_c, frame_stride=raw.stride(0) if raw.shape[0] > 1 else raw.shape[1], y=base,
+                     u=None if u_off is None else base + u_off, v=None if v_off is None else base + v_off,
+                     matrix=_YUV_MATRICES[matrix], full_range=int(bool(full_range)), dst=out.data_ptr(),
+                     dst_h=out.shape[1], dst_w=out.shape[2], flip=int(bool(flip)), dst_bgr=0)
+    L.check(L.load().ppn_ingest_yuv(d, L.current_stream_ptr()), "ppn_ingest_yuv")
+
+
+def ingest_yuv(raw: torch.Tensor, fmt: str, src_hw, size=384, out: Optional[torch.Tensor] = None, flip: bool = False,
+               matrix: str = "bt601", full_range: bool = False, pitch: Optional[int] = None) -> torch.Tensor:
+    """Raw video frames -> u8 RGB [B,h,w,3] in one launch (ppn_ingest_yuv): colour conversion (OpenCV's fixed-point
+    YUV -> RGB, `matrix` "bt601" / "bt709", limited or full range), the resize of ``ingest_frames`` and the optional flip
+    of both axes, without a full-resolution RGB copy.  `raw`: u8 CUDA tensor [B, nbytes], one contiguous frame per row
+    with the planes laid out as ``yuv_frame_layout(fmt, src_hw, pitch)`` says (`fmt` "nv12", "i420" or "yuyv"; `pitch`
+    bytes per luma row, tight by default; rows may be longer than a frame).  `size`: an int or (h, w).  `out` may be
+    ``model.input_buffer(...)`` exactly as for ``ingest_frames``."""
+    if not (isinstance(raw, torch.Tensor) and raw.is_cuda and raw.dtype == torch.uint8 and raw.dim() == 2):
+        raise ValueError("ingest_yuv expects a uint8 CUDA tensor [B, nbytes]")
+    if raw.stride(1) != 1:
+        raw = raw.contiguous()
+    h, w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    b = raw.shape[0]
+    if out is None:
+        out = torch.empty(b, h, w, 3, dtype=torch.uint8, device=raw.device)
+    if tuple(out.shape) != (b, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor {(b, h, w, 3)}")
+    _launch_ingest_yuv(raw, fmt, src_hw, out, flip, matrix, full_range, pitch)
+    return out
+
+
+def grab_frame_raw(cap, fmt: str, src_hw, size=384, out: Optional[torch.Tensor] = None, flip: bool = True,
+                   matrix: str = "bt601", full_range: bool = False, pitch: Optional[int] = None):
+    """``grab_frame`` for a capture that hands out raw frames (cv2 with CAP_PROP_CONVERT_RGB = 0, a pipe reader):
+    ``cap.read() -> (ret, u8 array of the frame's bytes, any shape)`` -- cv2 gives [H,W,2] for YUYV and [H*3/2,W] for
+    NV12 / I420.  Returns ``(ret, frame)``, frame a u8 RGB [1,h,w,3] CUDA tensor; `flip` defaults to grab_frame's."""
+    ret, frame = cap.read()
+    if not ret or frame is None:
+        return ret, None
+    f = np.ascontiguousarray(np.asarray(frame))
+    if f.dtype != np.uint8:
+        raise ValueError("cap.read() must deliver the raw frame as uint8")
+    raw = torch.from_numpy(f.reshape(1, -1)).cuda(non_blocking=True)
+    return ret, ingest_yuv(raw, fmt, src_hw, size, out, flip, matrix, full_range, pitch)
+
+
 def _decode_flip_averaged(frames: torch.Tensor, model: PoseProposalNet, decoder: Optional[D.Decoder],
                           detection_thresh: float, merger=None) -> D.DecodeResult:
     """Horizontal-flip test-time averaging (tta.py): [frames | frames mirrored] staged straight into the plan's input of
@@ -302,6 +384,8 @@ class MultiLaneInference:
                          for _ in range(lanes)]
         self.streams = _lane_streams(dev, lanes)
         self._stages = [None] * lanes                     # pinned read-back buffers, created on first use
+        self._raw = [None] * lanes                        # device staging of raw video frames (submit_raw), likewise
+        self.insize_hw = (int(insize_hw[0]), int(insize_hw[1]))
         self.k = 0
         # tile_policy 1: conv tiles chosen by efficiency alone instead of whole rounds of workgroups (process-wide
         # setting of libppn, restored by close()); measured +4 % with two lanes, but the per-launch (one in flight)
@@ -354,6 +438,48 @@ class MultiLaneInference:
             else:
                 st.wait_event(ready)
             unary, keys = self.model.forward_u8(frames_u8, fused_decode=True, slot=k, conv_flags=self._conv_flags)
+            res = self.decoders[k].decode_fused(unary, keys)
+            if to_host:
+                if self._stages[k] is None:
+                    self._stages[k] = D.HostStage(self.decoders[k].batch, cap=min(64, self.decoders[k].out.max_humans))
+                res.hosted = res.to_host_async(self._stages[k])
+            ev = torch.cuda.Event()
+            ev.record(st)
+        res.ready = ev
+        return res
+
+    def submit_raw(self, raw: torch.Tensor, fmt: str, src_hw, to_host: bool = False, flip: bool = False,
+                   matrix: str = "bt601", full_range: bool = False, pitch: Optional[int] = None) -> D.DecodeResult:
+        """``submit`` for raw video frames (see ``ingest_yuv``): `raw` u8 [B, nbytes] on the device or in PINNED host
+        memory, in any source size.  Host bytes go H2D on the lane's stream into a raw staging buffer the lane owns
+        (1.5 or 2 bytes per source pixel instead of 3 per network pixel after a host conversion); ppn_ingest_yuv then
+        writes the lane's own input buffer and the forward and decode follow as in ``submit``."""
+        if not (isinstance(raw, torch.Tensor) and raw.dtype == torch.uint8 and raw.dim() == 2):
+            raise ValueError("submit_raw expects a uint8 tensor [B, nbytes]")
+        k = self.k
+        self.k = (k + 1) % len(self.streams)
+        st = self.streams[k]
+        on_host = not raw.is_cuda
+        if on_host:
+            if not raw.is_pinned():
+                raise ValueError("host frames must be in pinned memory (tensor.pin_memory())")
+        else:
+            if raw.stride(1) != 1:
+                raw = raw.contiguous()
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(raw.device))     # the frames are complete on the caller's stream
+        b, (h, w) = raw.shape[0], self.insize_hw
+        with torch.cuda.stream(st):
+            buf = self.model.input_buffer(b, h, w, True, True, slot=k, conv_flags=self._conv_flags)
+            if on_host:
+                if self._raw[k] is None or self._raw[k].shape != raw.shape:
+                    self._raw[k] = torch.empty(raw.shape, dtype=torch.uint8, device=buf.device)
+                self._raw[k].copy_(raw, non_blocking=True)
+                raw = self._raw[k]
+            else:
+                st.wait_event(ready)
+            _launch_ingest_yuv(raw, fmt, src_hw, buf, flip, matrix, full_range, pitch)
+            unary, keys = self.model.forward_u8(buf, fused_decode=True, slot=k, conv_flags=self._conv_flags)
             res = self.decoders[k].decode_fused(unary, keys)
             if to_host:
                 if self._stages[k] is None:
