@@ -474,6 +474,88 @@ int ppn_ingest_yuv(const ppn_ingest_desc* d, void* stream);
 int ppn_yuv_coefficients(int32_t matrix, int32_t full_range, int32_t out6[6]);   /* host only: the table above */
 
 /*
+ * Windowed inference (no counterpart in the reference, which squeezes every frame to the network's square input): a big
+ * frame is cut into up to PPN_MAX_WINDOWS overlapping windows, every window runs as one image of the batch, and the people
+ * of the windows are joined in frame pixels.  ONE layout serves every frame of a call (a fixed camera).  It is a host struct,
+ * validated on the host and handed to the kernels by value: no device table, no synchronisation.  Image f * n + i of the
+ * batch is window i of frame f.  A layout is bad (PPN_E_INVALID) when it is NULL, n is outside 1..PPN_MAX_WINDOWS, or a
+ * window has h < 1, w < 1, y0 < 0 or x0 < 0.  tests/windows_ref.py restates both entry points in NumPy; kernels and
+ * restatement agree on bytes.
+ */
+#define PPN_MAX_WINDOWS 16
+typedef struct ppn_window { int32_t y0, x0, h, w; } ppn_window;      /* source pixels */
+typedef struct ppn_window_layout { int32_t n; ppn_window win[PPN_MAX_WINDOWS]; } ppn_window_layout;
+
+/*
+ * ppn_ingest_windows (csrc/ingest.hip): the windows of F = d->batch raw frames into d->dst u8 [F * n][dst_h][dst_w][3], one
+ * launch.  NORMATIVE: every output byte equals what ppn_ingest_yuv writes for a picture that consists of the window alone --
+ * its planes cropped at (y0, x0) to h x w.  That covers the clamping of the taps at the WINDOW's borders (not the frame's),
+ * the exact-halving path chosen per window (h == 2 * dst_h && w == 2 * dst_w) beside bilinear windows of the same launch,
+ * the flip, dst_bgr and both store paths.  The per-axis scale is the host-computed double (double)w / (double)dst_w of the
+ * window (h / dst_h).
+ *
+ * A fourth pixel format, accepted by this entry only (ppn_ingest_yuv refuses it): PPN_PIX_BGR24, packed B, G, R u8 per
+ * pixel, y: [src_h][pitch] with pitch >= 3 * src_w, as cv2.VideoCapture delivers it; u, v, matrix and full_range are not
+ * read (matrix must still be 0 or 1).  The rule is ppn_ingest_frames on the cropped picture with swap_rb = !dst_bgr: a
+ * tap is the pixel's three bytes, there is no conversion.
+ *
+ * PPN_E_INVALID, before any launch: everything ppn_ingest_yuv refuses (for PPN_PIX_BGR24 the size may be odd); a bad
+ * layout; a window that is not inside the picture; an odd x0 or w in a YUV format; an odd y0 or h in NV12 / I420;
+ * F * n above 65535.  Runs on `stream`, allocates nothing, does not synchronise.
+ */
+#define PPN_PIX_BGR24 3
+int ppn_ingest_windows(const ppn_ingest_desc* d, const ppn_window_layout* lay, void* stream);
+
+/*
+ * ppn_merge_windows (csrc/windows.hip): the people of the F * n window images (a ppn_decode result whose boxes are network
+ * pixels of each image, inH x inW) -> per frame one people list in frame pixels, without the duplicates that overlapping
+ * windows produce.  Every f32 step below is one IEEE operation rounded on its own (no contraction, IEEE division).
+ *
+ *   1 candidates   of frame f: for i = 0 .. n-1 and p = 0 .. min(max(count[f*n+i], 0), max_humans) - 1 the people with
+ *                  kp_cell[f*n+i][p][0] >= 0 and a root score score[f*n+i][p][0] that is not NaN, in (i, p) order.  The
+ *                  first PPN_MERGE_MAX_CAND take part; more set PPN_MERGE_FLAG_CAND_OVERFLOW.
+ *   2 mapping      of window i: sy = (float)h / (float)inH, sx = (float)w / (float)inW; Y = y * sy + (float)y0 and
+ *                  X = x * sx + (float)x0 (a multiply, then an add) on all four numbers (ymin, xmin, ymax, xmax) of every
+ *                  present keypoint box.
+ *   3 order        descending root score, compared as f32 values (-0.0 == +0.0); equal scores by ascending (i, p).
+ *   4 greedy walk  in that order: candidate c is a DUPLICATE of the first kept candidate k before it with
+ *                  window(k) != window(c) and iou(root_k, root_c) >= merge_thr on the mapped root boxes; without such a k,
+ *                  c is KEPT.  iou is ppn_track_update's, operation for operation: areas a = (ymax - ymin) * (xmax - xmin),
+ *                  tl = the larger ymin / xmin, br = the smaller ymax / xmax, inter = ((br0 - tl0) * (br1 - tl1)) *
+ *                  [tl0 < br0 && tl1 < br1], iou = inter / ((a_k + a_c) - inter), a value that is not > 0 (a NaN included)
+ *                  counts as 0.0f.  People of one window never suppress each other (the decode's own NMS has judged them);
+ *                  duplicates suppress nobody.
+ *   5 output order the kept candidates, in walk order, are output people 0, 1, ...; out_count[f] = their number; the first
+ *                  max_out are written, more set PPN_MERGE_FLAG_OUT_OVERFLOW.
+ *   6 keypoints    keypoint 0 is always the keeper's.  For j >= 1 with fuse != 0: among the keeper and its duplicates, in
+ *                  walk order, that have keypoint j (kp_cell >= 0), the member with the largest score[j]; only a strictly
+ *                  larger score (f32 comparison) replaces an earlier member.  With fuse == 0 only the keeper's own keypoints.
+ *                  A written keypoint gets the member's mapped box, its score and out_src = i * max_humans + p of the
+ *                  member (>= 0, so out_src serves as kp_cell for ppn_draw_humans and ppn_track_update); an absent keypoint
+ *                  out_src = -1 and a zero box and score.  Rows at and above min(out_count[f], max_out) are not touched.
+ *
+ *   count i32 [F*n], kp_cell i32 [F*n][max_humans][K], bbox f32 [F*n][max_humans][K][4], score f32 [F*n][max_humans][K]
+ *   out_count i32 [F], out_src i32 [F][max_out][K], out_bbox f32 [F][max_out][K][4] (ymin, xmin, ymax, xmax),
+ *   out_score f32 [F][max_out][K], out_flags i32 [F] (written, not accumulated: the flags of this call)
+ * One launch on `stream` (one workgroup per frame), no allocation, no host synchronisation, no atomics, integer and bitwise
+ * reductions only: the call can be captured into a graph and two runs give identical bytes.  PPN_E_INVALID before anything
+ * is launched for: a NULL pointer; K outside 1..PPN_MAX_KP; inH, inW or max_out < 1; max_humans outside 1..1024; frames < 1;
+ * a bad layout; a merge_thr that is NaN; a bbox or out_bbox that is not 16-byte aligned.  Precondition: the boxes are finite;
+ * otherwise which people are kept is unspecified, but no access leaves the buffers.
+ */
+#define PPN_MERGE_MAX_CAND 512
+#define PPN_MERGE_FLAG_CAND_OVERFLOW 1
+#define PPN_MERGE_FLAG_OUT_OVERFLOW 2
+typedef struct ppn_merge_cfg {
+    int32_t K, inH, inW, max_humans, max_out;
+    float merge_thr;      /* default 0.3 = the decode's nms_thr */
+    int32_t fuse;         /* 1: a kept person takes keypoints from its duplicates */
+} ppn_merge_cfg;
+int ppn_merge_windows(const ppn_merge_cfg* cfg, const ppn_window_layout* lay, const int32_t* count, const int32_t* kp_cell,
+                      const float* bbox, const float* score, int32_t frames, int32_t* out_count, int32_t* out_src,
+                      float* out_bbox, float* out_score, int32_t* out_flags, void* stream);
+
+/*
  * Train-time augmentation on the device (aug.py:13-160: IAA + ToNormalizedTensor), csrc/augment.hip.  Coordinates are pixel
  * indices with pixel centres at integers.  Per image the HOST builds the forward map F (source point -> output point:
  * rotation + isotropic scale about ((w-1)/2, (h-1)/2), minus the crop's (left, top), centre-aligned resize

@@ -58,6 +58,9 @@ SOURCES = [
     # track.hip is bit-exact with a NumPy restatement at the IoU and keypoint-gate thresholds: dx*dx + dy*dy and
     # old + alpha * (new - old) uncontracted, the IoU's divide IEEE-rounded
     ("track.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
+    # windows.hip is bit-exact with a NumPy restatement at the merge threshold and in the mapped boxes: y * sy + y0
+    # uncontracted, the scales' and the IoU's divides IEEE-rounded
+    ("windows.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
 ]
 
 

@@ -7,6 +7,7 @@
 // Arithmetic: oracle/ingest_ref.py states the rule (OpenCV's 8-bit fixed-point bilinear; PARITY UNPINNED, cv2 is not
 // available in this image).
 #include "common.h"
+#include "windows.h"
 
 namespace {
 
@@ -86,7 +87,8 @@ extern "C" int ppn_ingest_frames(const void* src_bgr, int32_t batch, int32_t src
 // on the colour-converted full-resolution picture, so only the 4 taps an output pixel needs are converted (OpenCV's
 // fixed-point YUV -> RGB, saturated per tap, then the interpolation above).  One thread makes 4 consecutive pixels of a
 // row and stores them as three dwords where the row layout allows it; the taps are byte loads (planes of any alignment).
-// No LDS, no atomics; L2 serves the taps that neighbouring pixels share.
+// No LDS, no atomics; L2 serves the taps that neighbouring pixels share.  ppn_ingest_windows (further down) runs the same
+// body on windows of the frames, and on packed BGR (PPN_PIX_BGR24: the tap is the pixel's three bytes).
 namespace {
 
 // round(c * 2^20) of the three-decimal constants; row 0 is OpenCV's ITUR_BT_601_{CY,CVR,CVG,CUG,CUB} (color_yuv.simd.hpp)
@@ -133,6 +135,13 @@ __device__ __forceinline__ void yuv_bytes(const unsigned char* py, const unsigne
 template <int FMT>
 __device__ __forceinline__ void yuv_tap(const unsigned char* py, const unsigned char* pu, const unsigned char* pv,
                                         int pitch, int pitch_c, const YuvCoeff& k, int y, int x, int (&rgb)[3]) {
+    if (FMT == PPN_PIX_BGR24) {                           // packed B, G, R: the tap is the three bytes
+        const unsigned char* r = py + (size_t)y * pitch + 3 * x;
+        rgb[0] = r[2];
+        rgb[1] = r[1];
+        rgb[2] = r[0];
+        return;
+    }
     int Y, U, V;
     yuv_bytes<FMT>(py, pu, pv, pitch, pitch_c, y, x, Y, U, V);
     const int l = max(0, Y - k.yoff) * k.cy + (1 << 19), uu = U - 128, vv = V - 128;
@@ -141,17 +150,13 @@ __device__ __forceinline__ void yuv_tap(const unsigned char* py, const unsigned 
     rgb[2] = sat8((l + k.cub * uu) >> 20);
 }
 
+// Four consecutive pixels (oy, ox0 .. ox0 + 3) of output image `img` from the picture of Hs x Ws pixels whose planes start at
+// py / pu / pv: the whole body of both kernels below.  A window is a picture whose plane pointers are moved to its origin.
 template <int FMT>
-__global__ void __launch_bounds__(256)
-ingest_yuv_kernel(YuvSrc s, YuvCoeff k, unsigned char* __restrict__ dst, int Hs, int Ws, int Hd, int Wd, double scale_x,
-                  double scale_y, int flip, int bgr, int area2, int dwords) {
-    const int ox0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    const int oy = blockIdx.y * blockDim.y + threadIdx.y;
-    const int b = blockIdx.z;
-    if (ox0 >= Wd || oy >= Hd) return;
-    const unsigned char* py = s.y + (long long)b * s.frame_stride;
-    const unsigned char* pu = s.u ? s.u + (long long)b * s.frame_stride : nullptr;
-    const unsigned char* pv = s.v ? s.v + (long long)b * s.frame_stride : nullptr;
+__device__ __forceinline__ void yuv_quad(const unsigned char* py, const unsigned char* pu, const unsigned char* pv, int pitch,
+                                         int pitch_c, const YuvCoeff& k, unsigned char* __restrict__ dst, int img, int Hs,
+                                         int Ws, int Hd, int Wd, double scale_x, double scale_y, int flip, int bgr, int area2,
+                                         int dwords, int oy, int ox0) {
     const int ry = flip ? Hd - 1 - oy : oy;
     int y0, y1;
     Axis ay = {0, 0, 0};
@@ -179,10 +184,10 @@ ingest_yuv_kernel(YuvSrc s, YuvCoeff k, unsigned char* __restrict__ dst, int Hs,
             x1 = min(ax.s + 1, Ws - 1);
         }
         int p00[3], p01[3], p10[3], p11[3];
-        yuv_tap<FMT>(py, pu, pv, s.pitch, s.pitch_c, k, y0, x0, p00);
-        yuv_tap<FMT>(py, pu, pv, s.pitch, s.pitch_c, k, y0, x1, p01);
-        yuv_tap<FMT>(py, pu, pv, s.pitch, s.pitch_c, k, y1, x0, p10);
-        yuv_tap<FMT>(py, pu, pv, s.pitch, s.pitch_c, k, y1, x1, p11);
+        yuv_tap<FMT>(py, pu, pv, pitch, pitch_c, k, y0, x0, p00);
+        yuv_tap<FMT>(py, pu, pv, pitch, pitch_c, k, y0, x1, p01);
+        yuv_tap<FMT>(py, pu, pv, pitch, pitch_c, k, y1, x0, p10);
+        yuv_tap<FMT>(py, pu, pv, pitch, pitch_c, k, y1, x1, p11);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             int v;
@@ -196,7 +201,7 @@ ingest_yuv_kernel(YuvSrc s, YuvCoeff k, unsigned char* __restrict__ dst, int Hs,
             px[i * 3 + (bgr ? 2 - c : c)] = (unsigned char)sat8(v);
         }
     }
-    unsigned char* o = dst + (((size_t)b * Hd + oy) * Wd + ox0) * 3;
+    unsigned char* o = dst + (((size_t)img * Hd + oy) * Wd + ox0) * 3;
     if (dwords) {                                         // Wd % 4 == 0 and dst 4-byte aligned: o is, and all 4 pixels exist
         unsigned int* o4 = reinterpret_cast<unsigned int*>(o);
 #pragma unroll
@@ -211,6 +216,62 @@ ingest_yuv_kernel(YuvSrc s, YuvCoeff k, unsigned char* __restrict__ dst, int Hs,
     }
 }
 
+template <int FMT>
+__global__ void __launch_bounds__(256)
+ingest_yuv_kernel(YuvSrc s, YuvCoeff k, unsigned char* __restrict__ dst, int Hs, int Ws, int Hd, int Wd, double scale_x,
+                  double scale_y, int flip, int bgr, int area2, int dwords) {
+    const int ox0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const int oy = blockIdx.y * blockDim.y + threadIdx.y;
+    const int b = blockIdx.z;
+    if (ox0 >= Wd || oy >= Hd) return;
+    const unsigned char* py = s.y + (long long)b * s.frame_stride;
+    const unsigned char* pu = s.u ? s.u + (long long)b * s.frame_stride : nullptr;
+    const unsigned char* pv = s.v ? s.v + (long long)b * s.frame_stride : nullptr;
+    yuv_quad<FMT>(py, pu, pv, s.pitch, s.pitch_c, k, dst, b, Hs, Ws, Hd, Wd, scale_x, scale_y, flip, bgr, area2, dwords, oy,
+                  ox0);
+}
+
+// ---- windows of raw frames (include/ppn.h: ppn_ingest_windows) ---------------------------------------------------------
+// Image f * n + i is window i of frame f.  The layout travels by value in the kernel arguments (a uniform index: scalar
+// loads); per window the host supplies the two scales and the exact-halving choice.
+struct WinArgs {
+    int n;
+    ppn_window win[PPN_MAX_WINDOWS];
+    double scale_x[PPN_MAX_WINDOWS], scale_y[PPN_MAX_WINDOWS];
+    int area2[PPN_MAX_WINDOWS];
+};
+
+template <int FMT>
+__global__ void __launch_bounds__(256)
+ingest_windows_kernel(YuvSrc s, YuvCoeff k, WinArgs wa, unsigned char* __restrict__ dst, int Hd, int Wd, int flip, int bgr,
+                      int dwords) {
+    const int ox0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const int oy = blockIdx.y * blockDim.y + threadIdx.y;
+    const int img = blockIdx.z;
+    if (ox0 >= Wd || oy >= Hd) return;
+    const int f = img / wa.n, i = img - f * wa.n;
+    const ppn_window w = wa.win[i];
+    // the window's planes: y0 and x0 are even wherever chroma is shared, so sample (y >> 1, x >> 1) of the window is the
+    // frame's sample of the same pixel
+    const unsigned char* py = s.y + (long long)f * s.frame_stride + (long long)w.y0 * s.pitch;
+    const unsigned char *pu = nullptr, *pv = nullptr;
+    if (FMT == PPN_PIX_NV12) {
+        py += w.x0;
+        pu = s.u + (long long)f * s.frame_stride + (long long)(w.y0 >> 1) * s.pitch_c + w.x0;
+    } else if (FMT == PPN_PIX_I420) {
+        py += w.x0;
+        const long long o = (long long)f * s.frame_stride + (long long)(w.y0 >> 1) * s.pitch_c + (w.x0 >> 1);
+        pu = s.u + o;
+        pv = s.v + o;
+    } else if (FMT == PPN_PIX_YUYV) {
+        py += 2 * w.x0;
+    } else {
+        py += 3 * w.x0;
+    }
+    yuv_quad<FMT>(py, pu, pv, s.pitch, s.pitch_c, k, dst, img, w.h, w.w, Hd, Wd, wa.scale_x[i], wa.scale_y[i], flip, bgr,
+                  wa.area2[i], dwords, oy, ox0);
+}
+
 }  // namespace
 
 extern "C" int ppn_yuv_coefficients(int32_t matrix, int32_t full_range, int32_t out6[6]) {
@@ -220,37 +281,57 @@ extern "C" int ppn_yuv_coefficients(int32_t matrix, int32_t full_range, int32_t 
     return PPN_OK;
 }
 
-extern "C" int ppn_ingest_yuv(const ppn_ingest_desc* d, void* stream) {
-    if (!d) return ppn::fail(PPN_E_INVALID, "ppn_ingest_yuv: NULL descriptor");
+namespace {
+
+// The refusals both raw-frame entries share; `who` names the entry in the message.  bgr_ok: PPN_PIX_BGR24 is a format.
+int check_desc(const char* who, const ppn_ingest_desc* d, bool bgr_ok) {
+    if (!d) return ppn::fail(PPN_E_INVALID, "%s: NULL descriptor", who);
     const int fmt = d->format;
-    if (fmt != PPN_PIX_NV12 && fmt != PPN_PIX_I420 && fmt != PPN_PIX_YUYV)
-        return ppn::fail(PPN_E_INVALID, "ppn_ingest_yuv: unknown format %d", fmt);
-    if (d->matrix != 0 && d->matrix != 1) return ppn::fail(PPN_E_INVALID, "ppn_ingest_yuv: unknown matrix %d", d->matrix);
-    if (!d->dst || !d->y || (fmt != PPN_PIX_YUYV && !d->u) || (fmt == PPN_PIX_I420 && !d->v))
-        return ppn::fail(PPN_E_INVALID, "ppn_ingest_yuv: NULL buffer");
+    if (fmt != PPN_PIX_NV12 && fmt != PPN_PIX_I420 && fmt != PPN_PIX_YUYV && !(bgr_ok && fmt == PPN_PIX_BGR24))
+        return ppn::fail(PPN_E_INVALID, "%s: unknown format %d", who, fmt);
+    if (d->matrix != 0 && d->matrix != 1) return ppn::fail(PPN_E_INVALID, "%s: unknown matrix %d", who, d->matrix);
+    const bool is420 = fmt == PPN_PIX_NV12 || fmt == PPN_PIX_I420;
+    if (!d->dst || !d->y || (is420 && !d->u) || (fmt == PPN_PIX_I420 && !d->v))
+        return ppn::fail(PPN_E_INVALID, "%s: NULL buffer", who);
     if (d->batch < 1 || d->src_h < 1 || d->src_w < 1 || d->dst_h < 1 || d->dst_w < 1 || d->batch > 65535 ||
         d->dst_h > 65535 || d->src_h > 16384 || d->src_w > 16384)
-        return ppn::fail(PPN_E_INVALID, "ppn_ingest_yuv: bad geometry %d x %dx%d -> %dx%d", d->batch, d->src_h, d->src_w,
-                         d->dst_h, d->dst_w);
-    const bool is420 = fmt != PPN_PIX_YUYV;
-    if ((d->src_w & 1) || (is420 && (d->src_h & 1)))
-        return ppn::fail(PPN_E_INVALID, "ppn_ingest_yuv: odd source size %dx%d", d->src_h, d->src_w);
+        return ppn::fail(PPN_E_INVALID, "%s: bad geometry %d x %dx%d -> %dx%d", who, d->batch, d->src_h, d->src_w, d->dst_h,
+                         d->dst_w);
+    if (fmt != PPN_PIX_BGR24 && ((d->src_w & 1) || (is420 && (d->src_h & 1))))
+        return ppn::fail(PPN_E_INVALID, "%s: odd source size %dx%d", who, d->src_h, d->src_w);
     // bytes of one row and of one frame's plane (last row tight), luma / packed and chroma
-    const int64_t row = is420 ? d->src_w : 2 * (int64_t)d->src_w;
+    const int64_t row = is420 ? d->src_w : (fmt == PPN_PIX_YUYV ? 2 : 3) * (int64_t)d->src_w;
     const int64_t row_c = fmt == PPN_PIX_NV12 ? d->src_w : d->src_w / 2;
     if (d->pitch < row || (is420 && d->pitch_c < row_c))
-        return ppn::fail(PPN_E_INVALID, "ppn_ingest_yuv: pitch %d / %d below the row's %lld / %lld bytes", d->pitch,
-                         d->pitch_c, (long long)row, (long long)row_c);
+        return ppn::fail(PPN_E_INVALID, "%s: pitch %d / %d below the row's %lld / %lld bytes", who, d->pitch, d->pitch_c,
+                         (long long)row, (long long)row_c);
     const int64_t plane = (int64_t)(d->src_h - 1) * d->pitch + row;
     const int64_t plane_c = is420 ? (int64_t)(d->src_h / 2 - 1) * d->pitch_c + row_c : 0;
     if (d->frame_stride < plane || d->frame_stride < plane_c)
-        return ppn::fail(PPN_E_INVALID, "ppn_ingest_yuv: frame_stride %lld smaller than a plane (%lld bytes)",
+        return ppn::fail(PPN_E_INVALID, "%s: frame_stride %lld smaller than a plane (%lld bytes)", who,
                          (long long)d->frame_stride, (long long)(plane > plane_c ? plane : plane_c));
+    return PPN_OK;
+}
+
+YuvCoeff coeff_of(const ppn_ingest_desc* d) {
     const int32_t* c = kYuvCoeff[(d->full_range ? 2 : 0) + d->matrix];
-    const YuvCoeff k = {c[0], c[1], c[2], c[3], c[4], c[5]};
-    const YuvSrc s = {static_cast<const unsigned char*>(d->y), is420 ? static_cast<const unsigned char*>(d->u) : nullptr,
-                      fmt == PPN_PIX_I420 ? static_cast<const unsigned char*>(d->v) : nullptr, d->frame_stride, d->pitch,
-                      is420 ? d->pitch_c : 0};
+    return {c[0], c[1], c[2], c[3], c[4], c[5]};
+}
+
+YuvSrc planes_of(const ppn_ingest_desc* d) {
+    const bool is420 = d->format == PPN_PIX_NV12 || d->format == PPN_PIX_I420;
+    return {static_cast<const unsigned char*>(d->y), is420 ? static_cast<const unsigned char*>(d->u) : nullptr,
+            d->format == PPN_PIX_I420 ? static_cast<const unsigned char*>(d->v) : nullptr, d->frame_stride, d->pitch,
+            is420 ? d->pitch_c : 0};
+}
+
+}  // namespace
+
+extern "C" int ppn_ingest_yuv(const ppn_ingest_desc* d, void* stream) {
+    if (const int rc = check_desc("ppn_ingest_yuv", d, false)) return rc;
+    const int fmt = d->format;
+    const YuvCoeff k = coeff_of(d);
+    const YuvSrc s = planes_of(d);
     const int area2 = (d->src_h == 2 * d->dst_h && d->src_w == 2 * d->dst_w) ? 1 : 0;
     const int dwords = (d->dst_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d->dst) & 3) == 0) ? 1 : 0;
     // 32 x 8 threads = 128 x 8 output pixels per workgroup; a wave stores two 384-byte row pieces
@@ -268,3 +349,47 @@ extern "C" int ppn_ingest_yuv(const ppn_ingest_desc* d, void* stream) {
     PPN_LAUNCH_CHECK();
     return PPN_OK;
 }
+
+extern "C" int ppn_ingest_windows(const ppn_ingest_desc* d, const ppn_window_layout* lay, void* stream) {
+    static const char who[] = "ppn_ingest_windows";
+    if (const int rc = check_desc(who, d, true)) return rc;
+    if (const int rc = ppn::check_layout(who, lay)) return rc;
+    const int fmt = d->format;
+    const bool yuv = fmt != PPN_PIX_BGR24, is420 = fmt == PPN_PIX_NV12 || fmt == PPN_PIX_I420;
+    WinArgs wa;
+    wa.n = lay->n;
+    for (int i = 0; i < PPN_MAX_WINDOWS; ++i) {
+        const ppn_window w = i < lay->n ? lay->win[i] : lay->win[0];      // unused entries: a copy of the first
+        if (i < lay->n) {
+            if ((int64_t)w.y0 + w.h > d->src_h || (int64_t)w.x0 + w.w > d->src_w)
+                return ppn::fail(PPN_E_INVALID, "%s: window %d (%d, %d) %dx%d leaves the %dx%d picture", who, i, w.y0, w.x0,
+                                 w.h, w.w, d->src_h, d->src_w);
+            if ((yuv && ((w.x0 | w.w) & 1)) || (is420 && ((w.y0 | w.h) & 1)))
+                return ppn::fail(PPN_E_INVALID, "%s: window %d (%d, %d) %dx%d must be even where chroma is shared", who, i,
+                                 w.y0, w.x0, w.h, w.w);
+        }
+        wa.win[i] = w;
+        wa.scale_x[i] = (double)w.w / (double)d->dst_w;
+        wa.scale_y[i] = (double)w.h / (double)d->dst_h;
+        wa.area2[i] = (w.h == 2 * d->dst_h && w.w == 2 * d->dst_w) ? 1 : 0;
+    }
+    if ((int64_t)d->batch * lay->n > 65535)
+        return ppn::fail(PPN_E_INVALID, "%s: %d frames x %d windows exceed 65535 images", who, d->batch, lay->n);
+    const YuvCoeff k = coeff_of(d);
+    const YuvSrc s = planes_of(d);
+    const int dwords = (d->dst_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d->dst) & 3) == 0) ? 1 : 0;
+    const dim3 block(32, 8), grid((d->dst_w + 127) / 128, (d->dst_h + 7) / 8, d->batch * lay->n);
+    unsigned char* dst = static_cast<unsigned char*>(d->dst);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define PPN_WIN_LAUNCH(F)                                                                                                \
+    hipLaunchKernelGGL(ingest_windows_kernel<F>, grid, block, 0, st, s, k, wa, dst, d->dst_h, d->dst_w, d->flip ? 1 : 0, \
+                       d->dst_bgr ? 1 : 0, dwords)
+    if (fmt == PPN_PIX_NV12) PPN_WIN_LAUNCH(PPN_PIX_NV12);
+    else if (fmt == PPN_PIX_I420) PPN_WIN_LAUNCH(PPN_PIX_I420);
+    else if (fmt == PPN_PIX_YUYV) PPN_WIN_LAUNCH(PPN_PIX_YUYV);
+    else PPN_WIN_LAUNCH(PPN_PIX_BGR24);
+#undef PPN_WIN_LAUNCH
+    PPN_LAUNCH_CHECK();
+    return PPN_OK;
+}
+

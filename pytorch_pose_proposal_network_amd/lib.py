@@ -19,6 +19,9 @@ PPN_MATCH_FLAG_INDEX, PPN_MATCH_FLAG_GT_COUNT = 1, 2
 PPN_TRACK_SLOTS, PPN_TRACK_MAX_DET = 64, 256                                # ppn_track_update (csrc/track.hip)
 PPN_TRACK_FLAG_DET_OVERFLOW, PPN_TRACK_FLAG_SLOT_OVERFLOW = 1, 2
 PPN_PIX_NV12, PPN_PIX_I420, PPN_PIX_YUYV = 0, 1, 2                         # ppn_ingest_desc.format (csrc/ingest.hip)
+PPN_PIX_BGR24 = 3                                                           # ppn_ingest_windows only
+PPN_MAX_WINDOWS, PPN_MERGE_MAX_CAND = 16, 512                               # ppn_merge_windows (csrc/windows.hip)
+PPN_MERGE_FLAG_CAND_OVERFLOW, PPN_MERGE_FLAG_OUT_OVERFLOW = 1, 2
 PPN_STEM_RAW_S2 = 1 << 16          # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
 
 
@@ -143,6 +146,22 @@ class IngestDesc(C.Structure):
         ("frame_stride", C.c_int64), ("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p),
         ("matrix", C.c_int32), ("full_range", C.c_int32), ("dst", C.c_void_p)] + [
         (n, C.c_int32) for n in ("dst_h", "dst_w", "flip", "dst_bgr")]
+
+
+class Window(C.Structure):
+    """ppn_window: source pixels."""
+    _fields_ = [(n, C.c_int32) for n in ("y0", "x0", "h", "w")]
+
+
+class WindowLayout(C.Structure):
+    """ppn_window_layout: a host struct, handed to the kernels by value."""
+    _fields_ = [("n", C.c_int32), ("win", Window * PPN_MAX_WINDOWS)]
+
+
+class MergeCfg(C.Structure):
+    """ppn_merge_cfg (csrc/windows.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("K", "inH", "inW", "max_humans", "max_out")] + [
+        ("merge_thr", C.c_float), ("fuse", C.c_int32)]
 
 
 class PPNError(RuntimeError):
@@ -293,6 +312,9 @@ _SIGNATURES.update({
     "ppn_tta_stage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "ppn_track_update": (C.c_int, [C.POINTER(TrackCfg), C.POINTER(TrackState)] + [C.c_void_p] * 4 + [C.c_int32] * 3 +
                          [C.c_void_p] * 6),
+    "ppn_ingest_windows": (C.c_int, [C.POINTER(IngestDesc), C.POINTER(WindowLayout), C.c_void_p]),
+    "ppn_merge_windows": (C.c_int, [C.POINTER(MergeCfg), C.POINTER(WindowLayout)] + [C.c_void_p] * 4 + [C.c_int32] +
+                          [C.c_void_p] * 6),
 })
 
 EXPORTS = tuple(_SIGNATURES)

@@ -11,7 +11,8 @@ animation (rt_test.py:150-205) are out of scope.  ``inference`` returns the refe
 PIL image (pass ``draw=callable`` to post-process on the host); ``inference_drawn`` returns the drawn image as
 rt_test.inference does and ``inference_batch_drawn`` the drawn batch, both painted on the device (render.py,
 datatest.py:162-232).  ``inference_batch_tracked`` / ``inference_tracked`` add what the reference's loop lacks: ids that follow
-a person from frame to frame (track.py), again without reading the people lists back.
+a person from frame to frame (track.py), again without reading the people lists back.  ``inference_windows`` runs a big raw
+frame as overlapping windows of the batch and joins the people in frame pixels on the device (windows.py).
 """
 from __future__ import annotations
 
@@ -275,6 +276,39 @@ def inference_batch_tracked(frames_u8: torch.Tensor, model: PoseProposalNet, tra
     track.Tracker whose max_humans is the decoder's; it carries the tracks from call to call.  Nothing is read back."""
     res = inference_batch(frames_u8, model, decoder, detection_thresh, flip_tta, merger)
     return res, tracker.update(res)
+
+
+def inference_windows(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNet, layout, decoder: Optional[D.Decoder] = None,
+                      merger=None, detection_thresh: float = 0.15, size=384, flip: bool = False, matrix: str = "bt601",
+                      full_range: bool = False, pitch: Optional[int] = None, merge_thr: float = 0.3,
+                      fuse: bool = True) -> D.DecodeResult:
+    """Windowed inference (windows.py): the F raw frames `raw` (as ``windows.ingest_windows`` takes them; `fmt` "nv12",
+    "i420", "yuyv" or "bgr") are cut into the n windows of `layout` (a windows.WindowLayout of `src_hw`), ingested straight
+    into the plan's input buffer of batch F * n, run through the forward with fused decode, and the people of the windows
+    are joined on the device.  Returns the merged DecodeResult of F images in FRAME pixels (``kp_cell`` = the source person
+    of a keypoint, -1: absent); ``Tracker.update``, ``draw_people`` and ``to_humans()`` take it as it is.  Pass a Decoder
+    of batch F * n and a windows.WindowMerger to allocate nothing per call.  Nothing is read back.
+    ``flip=True`` (as ``ingest_yuv``: every image turned by 180 degrees) gives the people of the TURNED frame: each window
+    image is turned on its own, so window i lies at ``layout.flipped()``'s place in the turned frame and the merge runs
+    with that layout -- a `merger` passed in must then have been built on ``layout.flipped()``, and on `layout` otherwise."""
+    from . import windows as W
+    if tuple(int(v) for v in src_hw) != layout.src_hw:
+        raise ValueError(f"the layout cuts a {layout.src_hw} picture, the frames are {tuple(src_hw)}")
+    placed = layout.flipped() if flip else layout                    # where the window images lie in the frame the people are in
+    if merger is not None and (merger.layout.src_hw != placed.src_hw or merger.layout.windows != placed.windows):
+        raise ValueError("the merger's layout is not " + ("layout.flipped(), which flip=True needs" if flip else "the layout"))
+    h, w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    frames = raw.shape[0]
+    buf = model.input_buffer(frames * layout.n, h, w, True, True)
+    W.ingest_windows(raw, fmt, layout, (h, w), buf, flip, matrix, full_range, pitch)
+    unary, keys = model.forward_u8(buf, fused_decode=True)
+    if decoder is None:
+        decoder = D.Decoder(frames * layout.n, (unary.shape[2], unary.shape[3]), (h, w), model.local_grid_size,
+                            detection_thresh, device=unary.device)
+    res = decoder.decode_fused(unary, keys)
+    if merger is None:
+        merger = W.WindowMerger(placed, frames, (h, w), res.max_humans, merge_thr=merge_thr, fuse=fuse, device=unary.device)
+    return merger(res)
 
 
 def inference_tracked(image, model: PoseProposalNet, outsize, local_grid_size, tracker, detection_thresh: float = 0.15,
