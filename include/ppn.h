@@ -694,6 +694,72 @@ int ppn_draw_humans(const ppn_draw_cfg* cfg, const uint8_t* src, uint8_t* dst, i
                     void* stream);
 
 /*
+ * Drawing onto raw video surfaces (csrc/render.hip): the people painted straight onto NV12, I420 or YUYV frames -- what
+ * ppn_ingest_yuv reads -- in place or into a second surface, in one pass, without an RGB intermediate; the result is what
+ * an encoder or a raw pipe takes.  tests/render_yuv_ref.py restates both rules below in NumPy; kernel and restatement
+ * agree on every byte.
+ *
+ * Forward colour rule (NORMATIVE).  For a colour (R, G, B) and a set (matrix, range), all int32, arithmetic shift,
+ * sat8 = clamp to 0..255:
+ *     Y = sat8((CYR * R + CYG * G + CYB * B + (1 << 19) + (yoff << 20)) >> 20)
+ *     U = sat8((CUR * R + CUG * G + CUB * B + (1 << 19) + (128 << 20)) >> 20)
+ *     V = sat8((CVR * R + CVG * G + CVB * B + (1 << 19) + (128 << 20)) >> 20)
+ * The coefficients are round(c * 2^20) of the exact definitions Y' = Kr R + (1 - Kr - Kb) G + Kb B, U = (B - Y') / (2 (1 - Kb)),
+ * V = (R - Y') / (2 (1 - Kr)) with BT.601's Kr 0.299, Kb 0.114 and BT.709's Kr 0.2126, Kb 0.0722; limited range scales luma
+ * by 219 / 255 and chroma by 224 / 255, full range by 1 with yoff 0.  The G coefficient of U and of V is minus the sum of the
+ * other two, so every grey has U = V = 128 exactly.  No accumulator exceeds 2.7e8.
+ *     matrix, range          CYR     CYG     CYB       CUR      CUG     CUB      CVR      CVG     CVB   yoff
+ *     0 bt601, limited    269262  528618  102662   -155423  -305128  460551   460551  -385654  -74897     16   (the default)
+ *     1 bt709, limited    191455  644067   65019   -105533  -355018  460551   460551  -418321  -42230     16
+ *     0 bt601, full       313524  615514  119538   -176932  -347356  524288   524288  -439026  -85262      0
+ *     1 bt709, full       222927  749942   75707   -120138  -404150  524288   524288  -476214  -48074      0
+ * Full range reaches 256 before sat8 (pure blue's U, pure red's V); limited range stays within 16..235 (Y) and 16..240 (U, V).
+ * This is the project's own rule: it is NOT OpenCV's RGB -> YUV table (three-decimal constants) and NOT the algebraic inverse
+ * of ppn_ingest_yuv's rule, whose sets come from other constants -- a drawn colour read back through the ingest differs from
+ * the palette's by a few levels (profiles/render_yuv.txt).  ppn_rgb_to_yuv applies it on the host to n packed triples
+ * (rgb and yuv may be the same buffer); it needs no GPU.
+ *
+ * Paint rule (NORMATIVE).  Let P(y, x) be what ppn_draw_humans decides for a height x width frame: unpainted, or the RGB
+ * colour of the last covering primitive, the grid on top when enabled.  The palette and the grid's grey are converted once,
+ * on the host; the kernel does no colour arithmetic.
+ *   luma     sample (y, x) becomes Y(P(y, x)) where the pixel is painted and keeps the source byte otherwise.
+ *   chroma   a sample belongs to a group of pixels: the 2 x 2 block (2i .. 2i + 1, 2j .. 2j + 1) in NV12 / I420, the pair
+ *            (y, 2j .. 2j + 1) in YUYV.  With no painted pixel in the group it keeps the source bytes; otherwise U and V are
+ *            those of the colour of the FIRST painted pixel of the group in row-major order (the final colours: after all
+ *            people and the grid).  Not the top-left pixel alone, as OpenCV samples RGB -> YUV420: limbs are 2 pixels wide
+ *            and outlines 1, so an outline on an odd row or column would keep the background's chroma.
+ *   dst == src in every plane and in pitch, pitch_c and frame_stride: in place; only painted luma samples and the chroma
+ *            samples of groups with a painted pixel are stored.  Otherwise out of place: no dst plane may be a src plane (nor
+ *            overlap one), every content byte of every dst plane is written and the bytes between a row's content and its
+ *            pitch never are.  Unpainted samples are copied, never converted: repeated annotation does not degrade a picture.
+ * Planes are laid out as ppn_ingest_desc's (NV12: u = the interleaved UV plane, v = NULL; I420: YV12 swaps u and v; YUYV:
+ * y = the packed rows, u = v = NULL) and may have any alignment and pitch: out of place the kernel stores dwords (halfwords
+ * in I420's chroma planes) when width % 4 == 0 and every plane, pitch and frame_stride of both surfaces is a multiple of
+ * 4 (2 for I420's chroma), bytes otherwise -- the same bytes.
+ *
+ * PPN_E_INVALID, before any launch: everything ppn_draw_humans refuses (height and width are the surface's); a NULL surface
+ * or required plane; an unknown format (PPN_PIX_BGR24 included) or matrix; an odd width; an odd height in NV12 / I420; pitch or
+ * pitch_c below the row's bytes; frame_stride below a plane's bytes ((rows - 1) * pitch + row bytes); src and dst that differ
+ * in format, size, matrix or range; a dst plane equal to its src plane while another plane, a pitch or the stride differs.
+ * The size limits are ppn_draw_humans' (PPN_E_UNSUPPORTED).  workspace: ppn_draw_workspace_bytes.  Two launches on `stream`,
+ * no allocation, no host synchronisation.
+ */
+typedef struct ppn_yuv_surface {
+    int32_t format;        /* PPN_PIX_NV12, PPN_PIX_I420 or PPN_PIX_YUYV */
+    int32_t height, width;
+    int32_t pitch;         /* bytes per row of the Y plane, or of the packed row for YUYV */
+    int32_t pitch_c;       /* bytes per chroma row (NV12: >= width, I420: >= width / 2; ignored for YUYV) */
+    int64_t frame_stride;  /* bytes from one frame to the next, applied to each plane pointer */
+    void *y, *u, *v;
+    int32_t matrix;        /* 0 bt601, 1 bt709 */
+    int32_t full_range;
+} ppn_yuv_surface;
+int ppn_rgb_to_yuv(int32_t matrix, int32_t full_range, const uint8_t* rgb, uint8_t* yuv, int64_t n);   /* host only */
+int ppn_draw_humans_yuv(const ppn_draw_cfg* cfg, const ppn_yuv_surface* src, const ppn_yuv_surface* dst, int32_t batch,
+                        const int32_t* count, const int32_t* kp_cell, const float* bbox, int32_t max_humans, void* workspace,
+                        void* stream);
+
+/*
  * The per-image matching of a validation epoch on the device (main.py:1017-1172 validate / 886-1014 test_output ->
  * datatest.evaluation -> eval_helpers.assignGTmulti, eval_helpers.py:300-468), csrc/validate.hip: one batch of compact
  * people lists against the resident ground truth of the whole validation set, one workgroup per image, emitting the

@@ -13,6 +13,9 @@
 //                        from its last entry down and stops at the first primitive covering the pixel; a later chunk
 //                        overrides an earlier one.  In place only the drawn pixels are stored (3 bytes each); out of place
 //                        every pixel is written, 12 bytes per thread as three dwords when the rows allow it (V = 4).
+//   draw_raster_yuv_kernel   the same tiles, binning and resolve (the device function paint<V>) on raw NV12, I420 or YUYV
+//                        surfaces: luma per pixel, chroma per 2 x 2 group (per row pair in YUYV) from the group's first painted
+//                        pixel, exchanged between the two rows' lanes of a wave (ppn_draw_humans_yuv, further down).
 // All f32 arithmetic (midpoints, the scan line's x = (y - y0) * slope + x0, the slope's division) is written out in a fixed
 // order and the file is built with -ffp-contract=off and IEEE division.
 #include "common.h"
@@ -198,30 +201,29 @@ __device__ __forceinline__ unsigned cover(int4 p, int4 m, int px, int py, int H)
     }
 }
 
-struct RasterArgs {
-    const unsigned char* src;    // [B][H][W][3]
-    unsigned char* dst;
+// what the setup pass left for the raster pass, the frame's size and the grid
+struct PaintArgs {
     const int* count;
     const int4* bb;
     const int4* par;
     const int4* meta;
     int B, M, S, H, W, grid, grid_step;
+    unsigned grid_colour;        // packed like a primitive's colour
 };
 
-template <int V, bool INPLACE>
-__global__ void __launch_bounds__(THREADS) draw_raster_kernel(RasterArgs a) {
+constexpr unsigned GRID_RGB = 110u | 110u << 8 | 110u << 16;
+
+// What the people of image b and the grid paint on the pixels (px .. px + V - 1, py) of the tile at (tx0, ty0): bit j of
+// `hit` and col[j] (the primitive's packed colour) for the pixels of `inside`.  Every thread of the workgroup calls it:
+// there are barriers inside.
+template <int V>
+__device__ __forceinline__ void paint(const PaintArgs& a, int b, int tx0, int ty0, int px, int py, unsigned inside,
+                                      unsigned& hit, unsigned (&col)[V]) {
     __shared__ int4 s_bb[CAP], s_par[CAP], s_meta[CAP];
     __shared__ int s_wave[THREADS / 64];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int b = blockIdx.z;
-    const int tx0 = blockIdx.x * 32 * V, ty0 = blockIdx.y * TILE_H;
     const int tx1 = min(tx0 + 32 * V, a.W) - 1, ty1 = min(ty0 + TILE_H, a.H) - 1;
-    const int px = tx0 + (t & 31) * V, py = ty0 + (t >> 5);
-    unsigned inside = 0;
-#pragma unroll
-    for (int j = 0; j < V; ++j) inside |= (px + j < a.W && py < a.H) ? 1u << j : 0u;
-    unsigned hit = 0;
-    unsigned col[V];
+    hit = 0;
 #pragma unroll
     for (int j = 0; j < V; ++j) col[j] = 0;
 
@@ -282,25 +284,46 @@ __global__ void __launch_bounds__(THREADS) draw_raster_kernel(RasterArgs a) {
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             if ((inside >> j & 1) && ((px + j) % a.grid_step == 0 || py % a.grid_step == 0)) {
-                col[j] = 110u | 110u << 8 | 110u << 16;
+                col[j] = a.grid_colour;
                 hit |= 1u << j;
             }
         }
     }
+}
+
+struct RasterArgs {
+    const unsigned char* src;    // [B][H][W][3]
+    unsigned char* dst;
+    PaintArgs p;
+};
+
+template <int V, bool INPLACE>
+__global__ void __launch_bounds__(THREADS) draw_raster_kernel(RasterArgs ra) {
+    const PaintArgs& a = ra.p;
+    const int t = threadIdx.x;
+    const int b = blockIdx.z;
+    const int tx0 = blockIdx.x * 32 * V, ty0 = blockIdx.y * TILE_H;
+    const int px = tx0 + (t & 31) * V, py = ty0 + (t >> 5);
+    unsigned inside = 0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) inside |= (px + j < a.W && py < a.H) ? 1u << j : 0u;
+    unsigned hit;
+    unsigned col[V];
+    paint<V>(a, b, tx0, ty0, px, py, inside, hit, col);
 
     const size_t o = (((size_t)b * a.H + py) * a.W + px) * 3;
     if constexpr (INPLACE) {
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             if (hit >> j & 1) {
-                a.dst[o + 3 * j] = (unsigned char)col[j];
-                a.dst[o + 3 * j + 1] = (unsigned char)(col[j] >> 8);
-                a.dst[o + 3 * j + 2] = (unsigned char)(col[j] >> 16);
+                ra.dst[o + 3 * j] = (unsigned char)col[j];
+                ra.dst[o + 3 * j + 1] = (unsigned char)(col[j] >> 8);
+                ra.dst[o + 3 * j + 2] = (unsigned char)(col[j] >> 16);
             }
         }
     } else if constexpr (V == 4) {
         if (inside) {                                             // W % 4 == 0: the four pixels are in the frame together
-            const unsigned* s4 = reinterpret_cast<const unsigned*>(a.src + o);
+            const unsigned* s4 = reinterpret_cast<const unsigned*>(ra.src + o);
             unsigned q[3] = {s4[0], s4[1], s4[2]};
 #pragma unroll
             for (int n8 = 0; n8 < 12; ++n8) {                     // byte n8 of the twelve: channel n8 % 3 of pixel n8 / 3
@@ -309,17 +332,154 @@ __global__ void __launch_bounds__(THREADS) draw_raster_kernel(RasterArgs a) {
                     q[n8 / 4] = (q[n8 / 4] & ~(0xffu << (8 * (n8 % 4)))) | v << (8 * (n8 % 4));
                 }
             }
-            unsigned* d4 = reinterpret_cast<unsigned*>(a.dst + o);
+            unsigned* d4 = reinterpret_cast<unsigned*>(ra.dst + o);
             d4[0] = q[0]; d4[1] = q[1]; d4[2] = q[2];
         }
     } else {
         if (inside) {
             const bool h = hit & 1;
-            a.dst[o] = h ? (unsigned char)col[0] : a.src[o];
-            a.dst[o + 1] = h ? (unsigned char)(col[0] >> 8) : a.src[o + 1];
-            a.dst[o + 2] = h ? (unsigned char)(col[0] >> 16) : a.src[o + 2];
+            ra.dst[o] = h ? (unsigned char)col[0] : ra.src[o];
+            ra.dst[o + 1] = h ? (unsigned char)(col[0] >> 8) : ra.src[o + 1];
+            ra.dst[o + 2] = h ? (unsigned char)(col[0] >> 16) : ra.src[o + 2];
         }
     }
+}
+
+// ---- raw video surfaces (ppn_draw_humans_yuv) ------------------------------------------------------------------------
+// The same (hit, colour) pairs, the colours converted to Y | U << 8 | V << 16 on the host, stored into NV12, I420 or YUYV
+// planes.  A luma sample takes its own pixel's colour; a chroma sample the colour of the first painted pixel of its group
+// in row-major order.  A thread's four pixels are two column pairs; in NV12 / I420 the two rows of a 2 x 2 group are lanes
+// l and l ^ 32 of one wave (a tile starts on an even row), so one exchange of each pair's pick settles the group and the
+// even row's thread stores the sample.  MODE: in place (painted samples only, bytes), out of place as bytes, out of place
+// as dwords (halfwords for I420's chroma) when the host found every plane, pitch and stride of both surfaces aligned.
+enum { YUV_INPLACE = 0, YUV_BYTES = 1, YUV_WORDS = 2 };
+
+struct YuvPlanes {
+    unsigned char* y;
+    unsigned char* u;
+    unsigned char* v;
+    long long frame_stride;
+    int pitch, pitch_c;
+};
+
+struct YuvRasterArgs {
+    YuvPlanes src, dst;
+    PaintArgs p;
+};
+
+// N bytes at d: val[i] where bit i of `painted` is set, the source byte otherwise; only bytes of `valid` exist
+template <int N, int MODE>
+__device__ __forceinline__ void store_samples(unsigned char* d, const unsigned char* s, const unsigned (&val)[N],
+                                              unsigned painted, unsigned valid) {
+    if constexpr (MODE == YUV_INPLACE) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (painted >> i & 1) d[i] = (unsigned char)val[i];
+    } else if constexpr (MODE == YUV_BYTES) {
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (valid >> i & 1) d[i] = (painted >> i & 1) ? (unsigned char)val[i] : s[i];
+    } else if (valid) {                                           // width % 4 == 0: all N bytes are in the frame together
+        using word = std::conditional_t<N == 2, unsigned short, unsigned>;
+        constexpr int B = (int)sizeof(word);
+#pragma unroll
+        for (int w = 0; w < N / B; ++w) {
+            unsigned q = reinterpret_cast<const word*>(s)[w];
+#pragma unroll
+            for (int i = 0; i < B; ++i)
+                if (painted >> (w * B + i) & 1) q = (q & ~(0xffu << (8 * i))) | (val[w * B + i] & 0xffu) << (8 * i);
+            reinterpret_cast<word*>(d)[w] = (word)q;
+        }
+    }
+}
+
+template <int FMT, int MODE>
+__global__ void __launch_bounds__(THREADS) draw_raster_yuv_kernel(YuvRasterArgs ya) {
+    constexpr int V = 4;
+    const PaintArgs& a = ya.p;
+    const int t = threadIdx.x;
+    const int b = blockIdx.z;
+    const int tx0 = blockIdx.x * 32 * V, ty0 = blockIdx.y * TILE_H;
+    const int px = tx0 + (t & 31) * V, py = ty0 + (t >> 5);
+    unsigned inside = 0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) inside |= (px + j < a.W && py < a.H) ? 1u << j : 0u;
+    unsigned hit;
+    unsigned col[V];
+    paint<V>(a, b, tx0, ty0, px, py, inside, hit, col);
+
+    // per column pair g: bit 24 set and the colour of the first painted pixel of this row's pair, or 0
+    unsigned pick[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g)
+        pick[g] = (hit >> (2 * g) & 1) ? col[2 * g] | 1u << 24 : (hit >> (2 * g + 1) & 1) ? col[2 * g + 1] | 1u << 24 : 0u;
+    const unsigned pairs = (inside & 1) | (inside >> 1 & 2);      // bit g: pair g is in the frame (the width is even)
+    const long long so = (long long)b * ya.src.frame_stride, dof = (long long)b * ya.dst.frame_stride;
+
+    if constexpr (FMT == PPN_PIX_YUYV) {
+        unsigned val[8], painted = 0, valid = 0;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            val[4 * g] = col[2 * g] & 0xffu;
+            val[4 * g + 1] = pick[g] >> 8 & 0xffu;
+            val[4 * g + 2] = col[2 * g + 1] & 0xffu;
+            val[4 * g + 3] = pick[g] >> 16 & 0xffu;
+            painted |= ((hit >> (2 * g) & 1) | (pick[g] >> 24) << 1 | (hit >> (2 * g + 1) & 1) << 2 | (pick[g] >> 24) << 3) << (4 * g);
+            valid |= (pairs >> g & 1) ? 0xfu << (4 * g) : 0u;
+        }
+        const long long row = 2ll * px;
+        store_samples<8, MODE>(ya.dst.y + dof + (long long)py * ya.dst.pitch + row,
+                               ya.src.y + so + (long long)py * ya.src.pitch + row, val, painted, valid);
+    } else {
+        unsigned val[4];
+#pragma unroll
+        for (int j = 0; j < V; ++j) val[j] = col[j] & 0xffu;
+        store_samples<4, MODE>(ya.dst.y + dof + (long long)py * ya.dst.pitch + px,
+                               ya.src.y + so + (long long)py * ya.src.pitch + px, val, hit, inside);
+        unsigned below[2];
+#pragma unroll
+        for (int g = 0; g < 2; ++g) below[g] = (unsigned)__shfl_xor((int)pick[g], 32);
+        if ((t & 32) == 0) {                                      // the even row of the pair stores the group's sample
+            unsigned c[2], any = 0;
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                c[g] = pick[g] >> 24 ? pick[g] : below[g];
+                any |= (c[g] >> 24) << g;
+            }
+            const long long crow = py >> 1;
+            if constexpr (FMT == PPN_PIX_NV12) {
+                const unsigned uv[4] = {c[0] >> 8 & 0xffu, c[0] >> 16 & 0xffu, c[1] >> 8 & 0xffu, c[1] >> 16 & 0xffu};
+                const unsigned painted = (any & 1 ? 3u : 0u) | (any & 2 ? 12u : 0u);
+                const unsigned valid = (pairs & 1 ? 3u : 0u) | (pairs & 2 ? 12u : 0u);
+                store_samples<4, MODE>(ya.dst.u + dof + crow * ya.dst.pitch_c + px, ya.src.u + so + crow * ya.src.pitch_c + px,
+                                       uv, painted, valid);
+            } else {
+                const unsigned us[2] = {c[0] >> 8 & 0xffu, c[1] >> 8 & 0xffu}, vs[2] = {c[0] >> 16 & 0xffu, c[1] >> 16 & 0xffu};
+                const long long od = dof + crow * ya.dst.pitch_c + (px >> 1), os = so + crow * ya.src.pitch_c + (px >> 1);
+                store_samples<2, MODE>(ya.dst.u + od, ya.src.u + os, us, any, pairs);
+                store_samples<2, MODE>(ya.dst.v + od, ya.src.v + os, vs, any, pairs);
+            }
+        }
+    }
+}
+
+// the forward colour rule's sets (include/ppn.h), index (full_range ? 2 : 0) + matrix: CYR CYG CYB, CUR CUG CUB, CVR CVG CVB, yoff
+const int32_t kRgbToYuv[4][10] = {
+    {269262, 528618, 102662, -155423, -305128, 460551, 460551, -385654, -74897, 16},
+    {191455, 644067, 65019, -105533, -355018, 460551, 460551, -418321, -42230, 16},
+    {313524, 615514, 119538, -176932, -347356, 524288, 524288, -439026, -85262, 0},
+    {222927, 749942, 75707, -120138, -404150, 524288, 524288, -476214, -48074, 0},
+};
+
+inline int sat8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+
+// Y | U << 8 | V << 16 of one colour
+unsigned rgb_to_yuv(const int32_t* k, int r, int g, int b) {
+    const int h = 1 << 19;
+    const int y = sat8((k[0] * r + k[1] * g + k[2] * b + h + (k[9] << 20)) >> 20);
+    const int u = sat8((k[3] * r + k[4] * g + k[5] * b + h + (128 << 20)) >> 20);
+    const int v = sat8((k[6] * r + k[7] * g + k[8] * b + h + (128 << 20)) >> 20);
+    return (unsigned)y | (unsigned)u << 8 | (unsigned)v << 16;
 }
 
 int check_cfg(const ppn_draw_cfg* cfg, const char* who) {
@@ -336,6 +496,96 @@ int check_cfg(const ppn_draw_cfg* cfg, const char* who) {
     return PPN_OK;
 }
 
+
+// what both entries refuse of the people and the workspace; `who` names the entry in the message
+int check_call(const char* who, const ppn_draw_cfg* cfg, bool null_pointer, int batch, int height, int width, int max_humans,
+               const void* workspace) {
+    if (int rc = check_cfg(cfg, who)) return rc;
+    if (null_pointer) return ppn::fail(PPN_E_INVALID, "%s: NULL pointer", who);
+    if (batch < 1 || height < 1 || width < 1 || max_humans < 1)
+        return ppn::fail(PPN_E_INVALID, "%s: bad geometry (batch %d, %dx%d, max_humans %d)", who, batch, height, width,
+                         max_humans);
+    const int S = cfg->K + cfg->E;
+    const long long prims = (long long)batch * max_humans * S;
+    if (batch > 65535 || height > 32768 || width > 32768 || (long long)max_humans * S > 0x7fffffffLL / 2 ||
+        (prims + THREADS - 1) / THREADS > 0x7fffffffLL)
+        return ppn::fail(PPN_E_UNSUPPORTED, "%s: batch %d, frame %dx%d or %d people x %d slots beyond the limits", who, batch,
+                         height, width, max_humans, S);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) return ppn::fail(PPN_E_INVALID, "%s: workspace must be 16-byte aligned", who);
+    return PPN_OK;
+}
+
+// The setup launch with the palette as packed colours (RGB, or YUV for a raw surface); *p: what the raster pass needs.
+int launch_setup(const ppn_draw_cfg* cfg, const unsigned* colour, unsigned grid_colour, const int32_t* count,
+                 const int32_t* kp_cell, const float* bbox, int batch, int height, int width, int max_humans, void* workspace,
+                 hipStream_t st, PaintArgs* p) {
+    const int S = cfg->K + cfg->E;
+    const long long prims = (long long)batch * max_humans * S;
+    int4* ws = static_cast<int4*>(workspace);
+    SetupArgs sa{count, kp_cell, bbox, ws, ws + prims, ws + 2 * prims, batch, max_humans, cfg->K, cfg->E, height, width,
+                 cfg->visbbox ? 1 : 0, {}};
+    for (int i = 0; i < cfg->E; ++i) { sa.t.edge_src[i] = cfg->edge_src[i]; sa.t.edge_dst[i] = cfg->edge_dst[i]; }
+    for (int i = 0; i < cfg->K; ++i) {
+        sa.t.kp_order[i] = cfg->kp_order[i];
+        sa.t.colour[i] = colour[i];
+    }
+    draw_setup_kernel<<<(unsigned)((prims + THREADS - 1) / THREADS), THREADS, 0, st>>>(sa);
+    PPN_LAUNCH_CHECK();
+    *p = PaintArgs{count, sa.bb, sa.par, sa.meta, batch, max_humans, S, height, width, cfg->grid ? 1 : 0,
+                   cfg->grid ? cfg->grid_step : 1, grid_colour};
+    return PPN_OK;
+}
+
+// what ppn_draw_humans_yuv refuses of one surface
+int check_surface(const char* who, const char* name, const ppn_yuv_surface* s) {
+    if (!s) return ppn::fail(PPN_E_INVALID, "%s: NULL %s surface", who, name);
+    const int fmt = s->format;
+    if (fmt != PPN_PIX_NV12 && fmt != PPN_PIX_I420 && fmt != PPN_PIX_YUYV)
+        return ppn::fail(PPN_E_INVALID, "%s: %s: unknown format %d", who, name, fmt);
+    if (s->matrix != 0 && s->matrix != 1) return ppn::fail(PPN_E_INVALID, "%s: %s: unknown matrix %d", who, name, s->matrix);
+    const bool is420 = fmt != PPN_PIX_YUYV;
+    if (!s->y || (is420 && !s->u) || (fmt == PPN_PIX_I420 && !s->v)) return ppn::fail(PPN_E_INVALID, "%s: %s: NULL plane", who, name);
+    if (s->height < 1 || s->width < 1) return ppn::fail(PPN_E_INVALID, "%s: %s: bad size %dx%d", who, name, s->height, s->width);
+    if ((s->width & 1) || (is420 && (s->height & 1)))
+        return ppn::fail(PPN_E_INVALID, "%s: %s: odd size %dx%d", who, name, s->height, s->width);
+    const int64_t row = is420 ? s->width : 2 * (int64_t)s->width;
+    const int64_t row_c = fmt == PPN_PIX_NV12 ? s->width : s->width / 2;
+    if (s->pitch < row || (is420 && s->pitch_c < row_c))
+        return ppn::fail(PPN_E_INVALID, "%s: %s: pitch %d / %d below the row's %lld / %lld bytes", who, name, s->pitch, s->pitch_c,
+                         (long long)row, (long long)row_c);
+    const int64_t plane = (int64_t)(s->height - 1) * s->pitch + row;
+    const int64_t plane_c = is420 ? (int64_t)(s->height / 2 - 1) * s->pitch_c + row_c : 0;
+    if (s->frame_stride < plane || s->frame_stride < plane_c)
+        return ppn::fail(PPN_E_INVALID, "%s: %s: frame_stride %lld smaller than a plane (%lld bytes)", who, name,
+                         (long long)s->frame_stride, (long long)(plane > plane_c ? plane : plane_c));
+    return PPN_OK;
+}
+
+// every plane, pitch and stride of the surface allows the word stores of YUV_WORDS
+bool word_aligned(const ppn_yuv_surface* s) {
+    auto off = [](const void* p, int64_t a, int64_t b, uintptr_t n) {
+        return reinterpret_cast<uintptr_t>(p) % n || a % (int64_t)n || b % (int64_t)n;
+    };
+    if (s->width % 4 || off(s->y, s->pitch, s->frame_stride, 4)) return false;
+    if (s->format == PPN_PIX_NV12) return !off(s->u, s->pitch_c, s->frame_stride, 4);
+    if (s->format == PPN_PIX_I420) return !off(s->u, s->pitch_c, s->frame_stride, 2) && !off(s->v, s->pitch_c, s->frame_stride, 2);
+    return true;
+}
+
+YuvPlanes planes_of(const ppn_yuv_surface* s) {
+    const bool is420 = s->format != PPN_PIX_YUYV;
+    return {static_cast<unsigned char*>(s->y), is420 ? static_cast<unsigned char*>(s->u) : nullptr,
+            s->format == PPN_PIX_I420 ? static_cast<unsigned char*>(s->v) : nullptr, s->frame_stride, s->pitch,
+            is420 ? s->pitch_c : 0};
+}
+
+template <int FMT>
+void launch_yuv(int mode, dim3 grid, hipStream_t st, const YuvRasterArgs& ya) {
+    if (mode == YUV_INPLACE) draw_raster_yuv_kernel<FMT, YUV_INPLACE><<<grid, THREADS, 0, st>>>(ya);
+    else if (mode == YUV_WORDS) draw_raster_yuv_kernel<FMT, YUV_WORDS><<<grid, THREADS, 0, st>>>(ya);
+    else draw_raster_yuv_kernel<FMT, YUV_BYTES><<<grid, THREADS, 0, st>>>(ya);
+}
+
 }  // namespace
 
 extern "C" size_t ppn_draw_workspace_bytes(const ppn_draw_cfg* cfg, int32_t batch, int32_t max_humans) {
@@ -346,33 +596,16 @@ extern "C" size_t ppn_draw_workspace_bytes(const ppn_draw_cfg* cfg, int32_t batc
 extern "C" int ppn_draw_humans(const ppn_draw_cfg* cfg, const uint8_t* src, uint8_t* dst, int32_t batch, int32_t height,
                                int32_t width, const int32_t* count, const int32_t* kp_cell, const float* bbox,
                                int32_t max_humans, void* workspace, void* stream) {
-    if (int rc = check_cfg(cfg, "ppn_draw_humans")) return rc;
-    if (!src || !dst || !count || !kp_cell || !bbox || !workspace)
-        return ppn::fail(PPN_E_INVALID, "ppn_draw_humans: NULL pointer");
-    if (batch < 1 || height < 1 || width < 1 || max_humans < 1)
-        return ppn::fail(PPN_E_INVALID, "ppn_draw_humans: bad geometry (batch %d, %dx%d, max_humans %d)", batch, height, width,
-                         max_humans);
-    const int S = cfg->K + cfg->E;
-    const long long prims = (long long)batch * max_humans * S;
-    if (batch > 65535 || height > 32768 || width > 32768 || (long long)max_humans * S > 0x7fffffffLL / 2 ||
-        (prims + THREADS - 1) / THREADS > 0x7fffffffLL)
-        return ppn::fail(PPN_E_UNSUPPORTED, "ppn_draw_humans: batch %d, frame %dx%d or %d people x %d slots beyond the limits",
-                         batch, height, width, max_humans, S);
-    if (reinterpret_cast<uintptr_t>(workspace) % 16)
-        return ppn::fail(PPN_E_INVALID, "ppn_draw_humans: workspace must be 16-byte aligned");
+    if (int rc = check_call("ppn_draw_humans", cfg, !src || !dst || !count || !kp_cell || !bbox || !workspace, batch, height,
+                            width, max_humans, workspace))
+        return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int4* ws = static_cast<int4*>(workspace);
-    SetupArgs sa{count, kp_cell, bbox, ws, ws + prims, ws + 2 * prims, batch, max_humans, cfg->K, cfg->E, height, width,
-                 cfg->visbbox ? 1 : 0, {}};
-    for (int i = 0; i < cfg->E; ++i) { sa.t.edge_src[i] = cfg->edge_src[i]; sa.t.edge_dst[i] = cfg->edge_dst[i]; }
-    for (int i = 0; i < cfg->K; ++i) {
-        sa.t.kp_order[i] = cfg->kp_order[i];
-        sa.t.colour[i] = (unsigned)cfg->palette[i][0] | (unsigned)cfg->palette[i][1] << 8 | (unsigned)cfg->palette[i][2] << 16;
-    }
-    draw_setup_kernel<<<(unsigned)((prims + THREADS - 1) / THREADS), THREADS, 0, st>>>(sa);
-    PPN_LAUNCH_CHECK();
-    RasterArgs ra{src, dst, count, sa.bb, sa.par, sa.meta, batch, max_humans, S, height, width, cfg->grid ? 1 : 0,
-                  cfg->grid ? cfg->grid_step : 1};
+    unsigned colour[PPN_MAX_KP];
+    for (int i = 0; i < cfg->K; ++i)
+        colour[i] = (unsigned)cfg->palette[i][0] | (unsigned)cfg->palette[i][1] << 8 | (unsigned)cfg->palette[i][2] << 16;
+    RasterArgs ra{src, dst, {}};
+    if (int rc = launch_setup(cfg, colour, GRID_RGB, count, kp_cell, bbox, batch, height, width, max_humans, workspace, st, &ra.p))
+        return rc;
     const bool inplace = src == dst;
     const bool vec = width % 4 == 0 && reinterpret_cast<uintptr_t>(src) % 4 == 0 && reinterpret_cast<uintptr_t>(dst) % 4 == 0;
     const int V = inplace || vec ? 4 : 1;
@@ -380,6 +613,56 @@ extern "C" int ppn_draw_humans(const ppn_draw_cfg* cfg, const uint8_t* src, uint
     if (inplace) draw_raster_kernel<4, true><<<grid, THREADS, 0, st>>>(ra);
     else if (vec) draw_raster_kernel<4, false><<<grid, THREADS, 0, st>>>(ra);
     else draw_raster_kernel<1, false><<<grid, THREADS, 0, st>>>(ra);
+    PPN_LAUNCH_CHECK();
+    return PPN_OK;
+}
+
+extern "C" int ppn_rgb_to_yuv(int32_t matrix, int32_t full_range, const uint8_t* rgb, uint8_t* yuv, int64_t n) {
+    if (matrix != 0 && matrix != 1) return ppn::fail(PPN_E_INVALID, "ppn_rgb_to_yuv: unknown matrix %d", matrix);
+    if (n < 0 || (n > 0 && (!rgb || !yuv))) return ppn::fail(PPN_E_INVALID, "ppn_rgb_to_yuv: NULL pointer or negative count");
+    const int32_t* k = kRgbToYuv[(full_range ? 2 : 0) + matrix];
+    for (int64_t i = 0; i < n; ++i) {
+        const unsigned c = rgb_to_yuv(k, rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
+        yuv[3 * i] = (uint8_t)c;
+        yuv[3 * i + 1] = (uint8_t)(c >> 8);
+        yuv[3 * i + 2] = (uint8_t)(c >> 16);
+    }
+    return PPN_OK;
+}
+
+extern "C" int ppn_draw_humans_yuv(const ppn_draw_cfg* cfg, const ppn_yuv_surface* src, const ppn_yuv_surface* dst, int32_t batch,
+                                   const int32_t* count, const int32_t* kp_cell, const float* bbox, int32_t max_humans,
+                                   void* workspace, void* stream) {
+    const char* who = "ppn_draw_humans_yuv";
+    if (int rc = check_cfg(cfg, who)) return rc;
+    if (int rc = check_surface(who, "src", src)) return rc;
+    if (int rc = check_surface(who, "dst", dst)) return rc;
+    if (src->format != dst->format || src->height != dst->height || src->width != dst->width || src->matrix != dst->matrix ||
+        !src->full_range != !dst->full_range)
+        return ppn::fail(PPN_E_INVALID, "%s: src and dst differ in format, size, matrix or range", who);
+    const YuvPlanes ps = planes_of(src), pd = planes_of(dst);
+    const bool all = ps.y == pd.y && ps.u == pd.u && ps.v == pd.v && ps.pitch == pd.pitch && ps.pitch_c == pd.pitch_c &&
+                     ps.frame_stride == pd.frame_stride;
+    const bool any = ps.y == pd.y || (ps.u && ps.u == pd.u) || (ps.v && ps.v == pd.v);
+    if (any && !all)
+        return ppn::fail(PPN_E_INVALID, "%s: dst shares a plane with src but not every plane and the geometry (in place means all)",
+                         who);
+    if (int rc = check_call(who, cfg, !count || !kp_cell || !bbox || !workspace, batch, src->height, src->width, max_humans,
+                            workspace))
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int32_t* k = kRgbToYuv[(src->full_range ? 2 : 0) + src->matrix];
+    unsigned colour[PPN_MAX_KP];
+    for (int i = 0; i < cfg->K; ++i) colour[i] = rgb_to_yuv(k, cfg->palette[i][0], cfg->palette[i][1], cfg->palette[i][2]);
+    YuvRasterArgs ya{ps, pd, {}};
+    if (int rc = launch_setup(cfg, colour, rgb_to_yuv(k, 110, 110, 110), count, kp_cell, bbox, batch, src->height, src->width,
+                              max_humans, workspace, st, &ya.p))
+        return rc;
+    const int mode = all ? YUV_INPLACE : word_aligned(src) && word_aligned(dst) ? YUV_WORDS : YUV_BYTES;
+    const dim3 grid((src->width + 127) / 128, (src->height + TILE_H - 1) / TILE_H, batch);
+    if (src->format == PPN_PIX_NV12) launch_yuv<PPN_PIX_NV12>(mode, grid, st, ya);
+    else if (src->format == PPN_PIX_I420) launch_yuv<PPN_PIX_I420>(mode, grid, st, ya);
+    else launch_yuv<PPN_PIX_YUYV>(mode, grid, st, ya);
     PPN_LAUNCH_CHECK();
     return PPN_OK;
 }

@@ -123,6 +123,13 @@ class DrawCfg(C.Structure):
                 ("grid_step", C.c_int32)]
 
 
+class YuvSurface(C.Structure):
+    """ppn_yuv_surface (csrc/render.hip: ppn_draw_humans_yuv)."""
+    _fields_ = [(n, C.c_int32) for n in ("format", "height", "width", "pitch", "pitch_c")] + [
+        ("frame_stride", C.c_int64), ("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p),
+        ("matrix", C.c_int32), ("full_range", C.c_int32)]
+
+
 class TtaCfg(C.Structure):
     """ppn_tta_cfg (csrc/tta.hip)."""
     _fields_ = [(n, C.c_int32) for n in ("K", "E", "sH", "sW", "H", "W")] + [
@@ -306,6 +313,9 @@ _SIGNATURES.update({
     "ppn_draw_workspace_bytes": (C.c_size_t, [C.POINTER(DrawCfg), C.c_int32, C.c_int32]),
     "ppn_draw_humans": (C.c_int, [C.POINTER(DrawCfg), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ppn_rgb_to_yuv": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),    # host pointers
+    "ppn_draw_humans_yuv": (C.c_int, [C.POINTER(DrawCfg), C.POINTER(YuvSurface), C.POINTER(YuvSurface), C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ppn_pckh_match": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_float] + [C.c_void_p] * 5),
     "ppn_tta_merge": (C.c_int, [C.POINTER(TtaCfg), C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4),

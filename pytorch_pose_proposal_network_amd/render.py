@@ -3,6 +3,8 @@
 * ``draw_people(frames_u8, result)``     -- the device path: u8 RGB frames [B,H,W,3] + the DecodeResult as it lives on the
                                             device -> drawn frames, on the current stream, no host synchronisation.
 * ``Renderer(batch, max_humans)``        -- owns the workspace for a fixed geometry so repeated calls allocate nothing.
+* ``Renderer.draw_yuv(raw, fmt, src_hw, result)`` / ``draw_people_yuv`` -- the same people painted straight onto raw NV12 /
+                                            I420 / YUYV frames (ppn_draw_humans_yuv), in place or into a second surface.
 * ``draw_humans(keypoint_names, edges, pil_image, humans, ...)`` -- same name / arguments / return as datatest.py:162.
 
 The pixels are the ones PIL's ImageDraw paints for the reference's calls (rules and deviations: include/ppn.h,
@@ -84,15 +86,21 @@ class Renderer:
         in place; any other `out` is overwritten entirely.  gridOn adds the reference's cell grid with step
         int(W / outW), `outsize` = (outW, outH) defaulting to config.OUTSIZE.  Returns the drawn tensor."""
         _check_frames(frames_u8, out)
-        B, H, W, _ = frames_u8.shape
+        step = int(frames_u8.shape[2] / (outsize if outsize is not None else cfg.OUTSIZE)[0]) if gridOn else 1
+        return self._draw_rgb(frames_u8, result, make_cfg(visbbox, gridOn, step, palette), out)
+
+    def _check_result(self, B: int, result: D.DecodeResult):
         m = result.max_humans
         if B != self.batch or m != self.max_humans:
             raise ValueError(f"renderer built for batch {self.batch} x {self.max_humans} people, got {B} x {m}")
         if tuple(result.count.shape) != (B,) or tuple(result.kp_cell.shape) != (B, m, cfg.K) or \
                 tuple(result.bbox.shape) != (B, m, cfg.K, 4):
             raise ValueError("result does not hold count [B], kp_cell [B,M,K] and bbox [B,M,K,4]")
-        step = int(W / (outsize if outsize is not None else cfg.OUTSIZE)[0]) if gridOn else 1
-        c = make_cfg(visbbox, gridOn, step, palette)
+
+    def _draw_rgb(self, frames_u8: torch.Tensor, result: D.DecodeResult, c: L.DrawCfg, out: Optional[torch.Tensor]):
+        B, H, W, _ = frames_u8.shape
+        self._check_result(B, result)
+        m = result.max_humans
         if out is None:
             out = torch.empty_like(frames_u8)
         elif out.data_ptr() != frames_u8.data_ptr():
@@ -103,6 +111,79 @@ class Renderer:
                                          result.count.data_ptr(), result.kp_cell.data_ptr(), result.bbox.data_ptr(), m,
                                          self.workspace.data_ptr(), L.current_stream_ptr()), "ppn_draw_humans")
         return out
+
+    def draw_yuv(self, raw: torch.Tensor, fmt: str, src_hw, result: D.DecodeResult, visbbox: bool = False,
+                 grid_step: int = 0, out: Optional[torch.Tensor] = None, palette=None, pitch: Optional[int] = None,
+                 matrix: str = "bt601", full_range: bool = False) -> torch.Tensor:
+        """Draw `result`'s people (frame pixels, e.g. ``rt.inference_windows``' result) straight onto raw video frames
+        (ppn_draw_humans_yuv: no RGB intermediate, unpainted samples keep their bytes).  `raw`: u8 CUDA tensor [F, nbytes],
+        one frame per row laid out as ``rt.yuv_frame_layout(fmt, src_hw, pitch)`` says (`fmt` "nv12", "i420" or "yuyv";
+        rows may be longer than a frame); `matrix` / `full_range` name the surface's colour set as for ``rt.ingest_yuv``.
+        out=raw: in place.  out=None: a new tensor of raw's shape -- a copy of raw (the bytes outside the frames' content
+        included) that is then drawn in place.  Any other `out` must have raw's shape and not overlap it; the kernel writes
+        every content byte of it and nothing else.  grid_step > 0 adds the grid at that step.  `fmt` "bgr": packed BGR
+        frames [F, H * W * 3] (or [F, H, W, 3]) of tight pitch, served by the RGB rasteriser with the palette's channels
+        swapped.  Returns the drawn tensor."""
+        from . import rt
+        if not (isinstance(raw, torch.Tensor) and raw.is_cuda and raw.dtype == torch.uint8):
+            raise ValueError("draw_yuv expects a uint8 CUDA tensor")
+        H, W = int(src_hw[0]), int(src_hw[1])
+        grid_step = int(grid_step)
+        if grid_step < 0:
+            raise ValueError(f"grid_step {grid_step} < 0")
+        if fmt == "bgr":
+            if pitch is not None and int(pitch) != 3 * W:
+                raise ValueError(f"bgr frames are drawn at the tight pitch {3 * W} only, not {pitch}")
+            shape = (raw.shape[0], H, W, 3)
+            if not raw.is_contiguous() or raw.numel() != raw.shape[0] * H * W * 3:
+                raise ValueError(f"bgr frames must be contiguous with {H * W * 3} bytes each")
+            if out is not None and (not isinstance(out, torch.Tensor) or out.shape != raw.shape):
+                raise ValueError("out must have raw's shape")
+            swapped = [tuple(c)[::-1] for c in (default_palette() if palette is None else palette)]
+            frames, to = raw.view(shape), None if out is None else out.view(shape)
+            _check_frames(frames, to)
+            drawn = self._draw_rgb(frames, result, make_cfg(visbbox, grid_step > 0, grid_step, swapped), to)
+            return drawn.view(raw.shape) if out is None else out
+        if matrix not in rt._YUV_MATRICES:
+            raise ValueError(f"matrix must be one of {sorted(rt._YUV_MATRICES)}, not {matrix!r}")
+        nbytes, pitch, pitch_c, u_off, v_off = rt.yuv_frame_layout(fmt, (H, W), pitch)
+        if raw.dim() != 2 or raw.stride(1) != 1 or raw.shape[1] < nbytes:
+            raise ValueError(f"{fmt} frames of {(H, W)} with pitch {pitch} must be u8 [F, >= {nbytes}] with rows of unit stride")
+        F, m = raw.shape[0], result.max_humans
+        self._check_result(F, result)
+        c = make_cfg(visbbox, grid_step > 0, grid_step, palette)
+        if out is None:
+            out = raw = raw.clone()
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == raw.device and
+                  out.shape == raw.shape and out.stride(1) == 1):
+            raise ValueError("out must be a uint8 tensor of raw's shape on its device with rows of unit stride")
+        elif out.data_ptr() != raw.data_ptr() or out.stride(0) != raw.stride(0):
+            span = lambda t: (t.data_ptr(), t.data_ptr() + (t.shape[0] - 1) * t.stride(0) + t.shape[1])
+            (a0, a1), (b0, b1) = span(raw), span(out)
+            if a0 < b1 and b0 < a1:
+                raise ValueError("out must be raw itself or not overlap it")
+
+        def surface(t):
+            base = t.data_ptr()
+            return L.YuvSurface(format=rt._PIX_FORMATS[fmt], height=H, width=W, pitch=pitch, pitch_c=pitch_c,
+                                frame_stride=t.stride(0) if F > 1 else t.shape[1], y=base,
+                                u=None if u_off is None else base + u_off, v=None if v_off is None else base + v_off,
+                                matrix=rt._YUV_MATRICES[matrix], full_range=int(bool(full_range)))
+        L.check(self.lib.ppn_draw_humans_yuv(C.byref(c), C.byref(surface(raw)), C.byref(surface(out)), F,
+                                             result.count.data_ptr(), result.kp_cell.data_ptr(), result.bbox.data_ptr(), m,
+                                             self.workspace.data_ptr(), L.current_stream_ptr()), "ppn_draw_humans_yuv")
+        return out
+
+
+def draw_people_yuv(raw: torch.Tensor, fmt: str, src_hw, result: D.DecodeResult, visbbox: bool = False, grid_step: int = 0,
+                    out: Optional[torch.Tensor] = None, palette=None, pitch: Optional[int] = None, matrix: str = "bt601",
+                    full_range: bool = False) -> torch.Tensor:
+    """One-off ``Renderer.draw_yuv`` call (allocates the workspace; keep a Renderer for repeated use).  Runs on the current
+    stream without a host synchronisation."""
+    if not (isinstance(raw, torch.Tensor) and raw.is_cuda and raw.dim() >= 2):
+        raise ValueError("draw_people_yuv expects a uint8 CUDA tensor [F, nbytes]")
+    return Renderer(raw.shape[0], result.max_humans, raw.device).draw_yuv(raw, fmt, src_hw, result, visbbox, grid_step, out,
+                                                                          palette, pitch, matrix, full_range)
 
 
 def draw_people(frames_u8: torch.Tensor, result: D.DecodeResult, visbbox: bool = False, gridOn: bool = False,

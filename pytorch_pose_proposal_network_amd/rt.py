@@ -12,7 +12,8 @@ PIL image (pass ``draw=callable`` to post-process on the host); ``inference_draw
 rt_test.inference does and ``inference_batch_drawn`` the drawn batch, both painted on the device (render.py,
 datatest.py:162-232).  ``inference_batch_tracked`` / ``inference_tracked`` add what the reference's loop lacks: ids that follow
 a person from frame to frame (track.py), again without reading the people lists back.  ``inference_windows`` runs a big raw
-frame as overlapping windows of the batch and joins the people in frame pixels on the device (windows.py).
+frame as overlapping windows of the batch and joins the people in frame pixels on the device (windows.py);
+``inference_windows_drawn`` paints them straight onto the raw frames (render.Renderer.draw_yuv).
 """
 from __future__ import annotations
 
@@ -286,7 +287,7 @@ def inference_windows(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNe
     "i420", "yuyv" or "bgr") are cut into the n windows of `layout` (a windows.WindowLayout of `src_hw`), ingested straight
     into the plan's input buffer of batch F * n, run through the forward with fused decode, and the people of the windows
     are joined on the device.  Returns the merged DecodeResult of F images in FRAME pixels (``kp_cell`` = the source person
-    of a keypoint, -1: absent); ``Tracker.update``, ``draw_people`` and ``to_humans()`` take it as it is.  Pass a Decoder
+    of a keypoint, -1: absent); ``Tracker.update``, ``draw_people``, ``draw_people_yuv`` and ``to_humans()`` take it as it is.  Pass a Decoder
     of batch F * n and a windows.WindowMerger to allocate nothing per call.  Nothing is read back.
     ``flip=True`` (as ``ingest_yuv``: every image turned by 180 degrees) gives the people of the TURNED frame: each window
     image is turned on its own, so window i lies at ``layout.flipped()``'s place in the turned frame and the merge runs
@@ -309,6 +310,27 @@ def inference_windows(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNe
     if merger is None:
         merger = W.WindowMerger(placed, frames, (h, w), res.max_humans, merge_thr=merge_thr, fuse=fuse, device=unary.device)
     return merger(res)
+
+
+def inference_windows_drawn(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNet, layout, decoder: Optional[D.Decoder] = None,
+                            merger=None, detection_thresh: float = 0.15, size=384, flip: bool = False, matrix: str = "bt601",
+                            full_range: bool = False, pitch: Optional[int] = None, merge_thr: float = 0.3, fuse: bool = True,
+                            renderer=None, out: Optional[torch.Tensor] = None, visbbox: bool = False):
+    """inference_windows plus the drawing, all on the device: the merged people painted straight onto the raw frames they
+    were found in (``render.Renderer.draw_yuv``: NV12 / I420 / YUYV surfaces without an RGB intermediate, `matrix` and
+    `full_range` naming the surface's colours as they do for the ingest; "bgr" through the RGB rasteriser) ->
+    (DecodeResult, drawn raw frames).  `out` as in draw_yuv (None: a new tensor, `raw` itself: in place); pass a Decoder, a
+    windows.WindowMerger and a render.Renderer of (F, merged max_humans) to allocate nothing per call.  Nothing is read back.
+    ``flip=True`` raises ValueError: the people of a turned frame do not lie on the unturned surface."""
+    from . import render as R
+    if flip:
+        raise ValueError("inference_windows_drawn: flip=True gives the people of the turned frame, which do not lie on `raw`")
+    res = inference_windows(raw, fmt, src_hw, model, layout, decoder, merger, detection_thresh, size, False, matrix,
+                            full_range, pitch, merge_thr, fuse)
+    if renderer is None:
+        renderer = R.Renderer(raw.shape[0], res.max_humans, raw.device)
+    return res, renderer.draw_yuv(raw, fmt, src_hw, res, visbbox=visbbox, out=out, pitch=pitch, matrix=matrix,
+                                  full_range=full_range)
 
 
 def inference_tracked(image, model: PoseProposalNet, outsize, local_grid_size, tracker, detection_thresh: float = 0.15,
