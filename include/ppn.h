@@ -270,7 +270,7 @@ typedef struct ppn_conv_desc {
      * lists the two ranges as separate entries so that each launch is timed and named). */
     int32_t m_begin, m_count;
     /* Edge-aligned limb part of the head conv (the fast fused path): limb_edge_pad = 448 (the only size built: windows of
-     * 385..448 values, e.g. 21 x 21 = 441) says that `weight`, `scale1` and `shift1` hold ONLY the limb channels, edge e's
+     * 433..448 values, e.g. 21 x 21 = 441; any other window is PPN_E_UNSUPPORTED) says that `weight`, `scale1` and `shift1` hold ONLY the limb channels, edge e's
      * window in rows [e * limb_edge_pad, e * limb_edge_pad + limb_window) and padding after it (cout = E * limb_window,
      * cout_pad = E * limb_edge_pad).  One workgroup then owns a whole window of 128 cells, reduces its arg-max on the
      * accumulators and STORES argmax_keys u64 [B,E,H,W] (same key format; no atomics, the buffer need not be zeroed).

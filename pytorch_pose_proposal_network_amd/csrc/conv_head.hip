@@ -7,6 +7,10 @@
 // is reduced on the accumulators and the key of every (image, edge, cell) is STORED: no atomics, no pre-zeroed key
 // buffer, no staging of the tile through LDS (the chunked epilogue of conv_big.hip spends more cycles on that than
 // on the K loop: 15.2 k vs 13.5 k).
+// Windows: 433..448 values.  The epilogue masks the pad rows of an edge's tile (rows window..447) in the last 16-row
+// channel tile of the last channel wave only (rows 432..447); a pad row below it would compete -- with the zero weights
+// and bias model.py packs it scores sigmoid(0) = 0.5 and wins every window whose real scores are all lower -- so
+// conv_route.cpp refuses every other window (they take the atomic-key epilogue of conv_big.hip).
 //
 //   workgroup  512 threads = 8 waves as 4 (channels) x 2 (pixels); wave tile 112 channels x 64 pixels = 7 x 4 MFMA
 //              16x16 tiles (112 accumulator registers); two waves per SIMD
@@ -311,7 +315,8 @@ __global__ void __launch_bounds__(64 * NW, 2) head_limb_argmax_kernel(HeadArgs a
                     for (int r = 0; r < 4; ++r) {
                         const int s = wc * (BC / WC) + i * 16 + 4 * fq + r;
                         float t = acc[i][j][r] + sh[i][r];
-                        if (i == TC - 1) t = s < window ? t : NEG;    // pad rows (only in the last channel tile) do not compete
+                        // pad rows do not compete; window >= 433 (conv_route.cpp): they all lie in the last channel tile
+                        if (i == TC - 1) t = s < window ? t : NEG;
                         qm2[j] = __builtin_amdgcn_fmed3f(qm[j], qm2[j], t);
                         const bool gt = t > qm[j];                    // strict: first maximum in ascending s
                         qm[j] = fmaxf(qm[j], t);

@@ -392,6 +392,12 @@ int route_segment(const ppn_conv_desc* d, const RouteKnobs& k, ConvSegment* s, l
             return ppn::fail(PPN_E_INVALID, "limb_edge_pad: needs %d rows per edge (window <= that), cout = E * window, "
                                             "cout_pad = E * limb_edge_pad, sigmoid, argmax_keys only (no out_raw / unary_out)",
                              kEdgeTileBC);
+        // the kernel's epilogue masks the rows past the window in the LAST 16-row channel tile of its last wave only: a pad row
+        // below that tile would compete (with zero weights and bias it wins every window whose scores are all below 0.5)
+        if (d->limb_window <= d->limb_edge_pad - 16)
+            return ppn::fail(PPN_E_UNSUPPORTED, "limb_edge_pad: limb_window %d is outside %d..%d (the edge tile masks pad rows in its "
+                                                "last 16 rows only; smaller windows take the atomic-key epilogue, limb_edge_pad = 0)",
+                             d->limb_window, d->limb_edge_pad - 15, d->limb_edge_pad);
         if (!d->src || !d->weight) return ppn::fail(PPN_E_INVALID, "NULL src/weight");
         if (d->ksize != 1 || d->stride != 1 || d->pad != 0 || d->scale1)
             return ppn::fail(PPN_E_UNSUPPORTED, "limb_edge_pad: the head conv is 1x1, stride 1, no padding, bias only (scale1 NULL)");

@@ -162,9 +162,10 @@ def weight_geometry(dtype: int, op: A.ConvOp):
 
 
 def head_edge_pad(mode: Mode, limb_window: int, enabled: bool = True) -> int:
-    """Rows per edge of the edge-aligned limb tile (448) when the limb window fits it (385..448 values, e.g. the
-    reference's 21 x 21), else 0: the chunked epilogue with atomicMax keys.  enabled=False forces the latter."""
-    if not enabled or not (384 < limb_window <= 448) or mode.compute_dtype == X3:
+    """Rows per edge of the edge-aligned limb tile (448) when the limb window is one it decides correctly (433..448 values,
+    e.g. the reference's 21 x 21: the kernel masks the pad rows of an edge's tile in its last 16 rows only, and the dispatch
+    refuses every other window), else 0: the chunked epilogue with atomicMax keys.  enabled=False forces the latter."""
+    if not enabled or not (432 < limb_window <= 448) or mode.compute_dtype == X3:
         return 0
     return 448 if L.conv_tiling(mode.compute_dtype, 512, 512, 1)[2] == 1 else 0
 

@@ -98,10 +98,11 @@ def run_conv(x, w, dtype, stride=1, dil=1, pad=0, s1=None, b1=None, act1=0, resi
         d.out_act = act.data_ptr()
     if argmax is not None:
         uch, win = argmax
-        unary = torch.full((B, uch, Ho, Wo), float("nan"), device=dev)
+        ubuf = torch.full((max(1, B * uch * Ho * Wo),), float("nan"), device=dev)     # (uch = 0: unary_out must still be given)
+        unary = ubuf[:B * uch * Ho * Wo].view(B, uch, Ho, Wo)
         keys = torch.zeros(B, (Cout - uch) // win, Ho, Wo, dtype=torch.int64, device=dev)
-        keep += [unary, keys]
-        d.unary_out, d.argmax_keys, d.unary_channels, d.limb_window = unary.data_ptr(), keys.data_ptr(), uch, win
+        keep += [ubuf, keys]
+        d.unary_out, d.argmax_keys, d.unary_channels, d.limb_window = ubuf.data_ptr(), keys.data_ptr(), uch, win
     kernels = []
     for lo, n, tile in (ranges if ranges is not None else [(0, 0, None)]):
         d.m_begin, d.m_count = lo, n
@@ -132,10 +133,15 @@ def run_conv(x, w, dtype, stride=1, dil=1, pad=0, s1=None, b1=None, act1=0, resi
     return out
 
 
-def run_edge_argmax(x, w, bias, dtype, uch, win, edge_pad=448):
+def run_edge_argmax(x, w, bias, dtype, uch, win, edge_pad=448, pad_bias=1000.0, ranges=None, info=None):
     """The limb part of a conv3-shaped launch through the edge-aligned tile (ppn_conv_desc.limb_edge_pad): one channel
     tile per edge, arg-max reduced on the accumulators, keys STORED into a buffer that is NOT zeroed first.  x [B,Cin,H,W],
-    w [uch + E*win, Cin, 1, 1], bias [uch + E*win] CPU f32 -> (keys i64 [B,E,H,W] CPU, kernel name)."""
+    w [uch + E*win, Cin, 1, 1], bias [uch + E*win] CPU f32 -> (keys i64 [B,E,H,W] CPU, kernel name).
+
+    pad_bias: the bias of the rows of an edge's tile past its window (their weights are zero); 0.0 is what model.py packs.
+    bias=None: a NULL shift1.  ranges=[(m_begin, m_count), ...]: one launch per entry over that range of the flattened pixels.
+    info: a dict that receives "keys" (the DEVICE buffer, before the first launch: a caller that expects the launch to be refused
+    reads it afterwards) and, after the launches, "guard_ok": the garbage behind the key buffer is intact."""
     from pytorch_pose_proposal_network_amd import lib as L
     lib = L.load()
     dev = torch.device("cuda")
@@ -151,21 +157,33 @@ def run_edge_argmax(x, w, bias, dtype, uch, win, edge_pad=448):
     packed = torch.empty(E * edge_pad, ktot, dtype=tdt, device=dev)
     L.check(lib.ppn_pack_weight(dtype, we.data_ptr(), E * edge_pad, Cin, 1, E * edge_pad, ktot, korder, kstep,
                                 packed.data_ptr(), st))
-    be = torch.full((E, edge_pad), 1000.0)                     # a pad row that competed would win every window
-    be[:, :win] = bias[uch:].view(E, win)
-    be = be.view(-1).contiguous().to(dev)
+    be = None
+    if bias is not None:
+        be = torch.full((E, edge_pad), pad_bias)               # 1000: a pad row that competed would win every window
+        be[:, :win] = bias[uch:].view(E, win)
+        be = be.view(-1).contiguous().to(dev)
     xs = x.permute(0, 2, 3, 1).contiguous().to(dev, tdt)
     zero = torch.zeros(64, device=dev)
-    keys = torch.full((B, E, H, W), 0x7EADBEEF7EADBEEF, dtype=torch.int64, device=dev)   # garbage: must be overwritten
+    n_keys = B * E * H * W
+    # garbage: must be overwritten; as much again behind the buffer, where a row past M of the last pixel tile would land
+    kbuf = torch.full((2 * n_keys + 1024,), 0x7EADBEEF7EADBEEF, dtype=torch.int64, device=dev)
+    keys = kbuf[:n_keys].view(B, E, H, W)
+    if info is not None:
+        info["keys"] = keys
     d = L.ConvDesc()
     d.dtype, d.batch, d.in_h, d.in_w, d.cin = dtype, B, H, W, Cin
     d.out_h, d.out_w, d.cout = H, W, E * win
     d.ksize, d.stride, d.dilation, d.pad = 1, 1, 1, 0
     d.k_total, d.cout_pad, d.act1, d.out_nchw_f32 = ktot, E * edge_pad, 3, 1
-    d.src, d.weight, d.zero_page, d.shift1 = xs.data_ptr(), packed.data_ptr(), zero.data_ptr(), be.data_ptr()
+    d.src, d.weight, d.zero_page = xs.data_ptr(), packed.data_ptr(), zero.data_ptr()
+    d.shift1 = be.data_ptr() if be is not None else None
     d.argmax_keys, d.limb_window, d.limb_edge_pad = keys.data_ptr(), win, edge_pad
-    L.check(lib.ppn_conv2d_fused(C.byref(d), st), "ppn_conv2d_fused")
+    for lo, n in (ranges if ranges is not None else [(0, 0)]):
+        d.m_begin, d.m_count = lo, n
+        L.check(lib.ppn_conv2d_fused(C.byref(d), st), "ppn_conv2d_fused")
     torch.cuda.synchronize()
+    if info is not None:
+        info["guard_ok"] = bool((kbuf[n_keys:] == 0x7EADBEEF7EADBEEF).all())
     return keys.cpu(), lib.ppn_last_conv_kernel().decode()
 
 

@@ -255,9 +255,19 @@ def test_fused_decode_head_with_the_edge_tile(LW, mode_id):
     assert low.tensors["unary"] == ((2, N_UNARY, 6, 6), LW.F32) and low.tensors["keys"] == ((2, N_EDGES, 6, 6), LW.I64)
 
 
-@pytest.mark.parametrize("mode_id,grid", [("bf16", (9, 9)), ("f16", (9, 9)), ("x3", (21, 21)), ("bf16", (23, 23))])
+def test_head_edge_pad_takes_windows_433_to_448_only(LW):
+    """The edge-aligned tile masks pad rows in its last 16 rows only (csrc/conv_head.hip) and the dispatch refuses every other
+    window: the lowering must send exactly the windows 433 .. 448 to it."""
+    _, mode, _ = _lower(LW, "bf16", fused=True)
+    got = [LW.head_edge_pad(mode, w) for w in (1, 384, 385, 420, 431, 432, 433, 441, 447, 448, 449)]
+    assert got == [0, 0, 0, 0, 0, 0, 448, 448, 448, 448, 0]
+    assert LW.head_edge_pad(mode, 441, False) == 0
+
+
+@pytest.mark.parametrize("mode_id,grid", [("bf16", (9, 9)), ("f16", (9, 9)), ("x3", (21, 21)), ("bf16", (23, 23)),
+                                          ("bf16", (21, 20)), ("f16", (27, 16)), ("f32", (24, 18))])
 def test_fused_decode_head_with_atomic_keys(LW, mode_id, grid):
-    """A window outside 385..448 values (and the float16x3 mode): zero fill, then ONE head conv."""
+    """A window outside 433..448 values (and the float16x3 mode): zero fill, then ONE head conv."""
     ops, mode, low = _lower(LW, mode_id, fused=True, grid=grid)
     win = grid[0] * grid[1]
     ms, head = low.launches[-2:]

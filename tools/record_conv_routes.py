@@ -311,6 +311,8 @@ def negatives(L):
     neg(hd(), limb_edge_pad=256)
     neg(hd(), out_raw=P)
     neg(hd(), limb_window=449)
+    neg(valid(L, BF, 128, 432 * 2, **dict(head, cout_pad=896)), limb_window=432)                                 # pad rows below the last 16
+    neg(valid(L, BF, 128, 420 * 2, **dict(head, cout_pad=896)), limb_window=420)
     neg(hd(), act1=L.PPN_ACT_NONE)
     neg(hd(), cout_pad=1024)
     neg(hd(), src=None)
