@@ -556,6 +556,88 @@ int ppn_merge_windows(const ppn_merge_cfg* cfg, const ppn_window_layout* lay, co
                       float* out_bbox, float* out_score, int32_t* out_flags, void* stream);
 
 /*
+ * Person crops (no counterpart in the reference, which stops at the drawn frame): every detected person of a frame cut out
+ * of the RAW frame as a fixed-size picture for a following model.  Unlike a window layout the rectangles are DATA: a table
+ * in device memory that ppn_people_rois writes from the people lists and ppn_ingest_rois reads, so that decode -> ROIs ->
+ * crops is a chain of launches without a host synchronisation (it can be captured into a graph).  tests/crops_ref.py restates
+ * both entries in NumPy; kernels and restatement agree on bytes.
+ *
+ * ppn_people_rois (csrc/crops.hip): a decode result (count, kp_cell, bbox as ppn_merge_windows takes them; the scores are
+ * not read) -> roi i32 [F][max_rois][4] = (y0, x0, h, w) in source pixels and status i32 [F][max_rois].  Slot r of frame f
+ * is PERSON r of that frame: no sorting, no top-k, the first max_rois people are taken, so a tracker's ids[f][r], bbox[f][r]
+ * and crop r describe the same person.  The boxes are in pixels of some coordinate space (the network input for a plain
+ * decode, the frame itself after ppn_merge_windows); the host passes sy = (float)src_h / (float)space_h and sx likewise.
+ * Every f32 step below is one IEEE operation rounded on its own (no contraction, IEEE division).
+ *
+ *   1 person      slot r holds a person when r < min(max(count[f], 0), max_humans) and kp_cell[f][r][0] >= 0.  Otherwise
+ *                 status = PPN_ROI_EMPTY and the ROI is (0, 0, 0, 0).
+ *   2 box         mode PPN_ROI_MODE_ROOT: the root box bbox[f][r][0].  mode PPN_ROI_MODE_PEOPLE: the union of the boxes of
+ *                 all present keypoints (kp_cell[f][r][j] >= 0), the smaller ymin / xmin and the larger ymax / xmax in
+ *                 ascending j.  A number of a box that is used which is not finite makes the slot DEGENERATE (rule 7).
+ *   3 mapping     Y = y * sy, X = x * sx on the four numbers (ymin, xmin, ymax, xmax).
+ *   4 centre      cy = (ymin + ymax) * 0.5f;  hh = (ymax - ymin) * 0.5f;  hh = hh + hh * margin (a multiply, then an add);
+ *                 the same for x, giving cx and hw.
+ *   5 aspect      when aspect > 0 (the host's float dst_w / dst_h): if hw < hh * aspect then hw = hh * aspect, otherwise
+ *                 hh = hw / aspect.  aspect == 0: the box keeps its shape.
+ *   6 edges       t = floorf(cy - hh), b = ceilf(cy + hh), l = floorf(cx - hw), r = ceilf(cx + hw).  If one of the four is
+ *                 not finite: DEGENERATE.  Each is limited to the picture as a float, fminf(fmaxf(v, 0), (float)src_h) for
+ *                 rows, src_w for columns, and converted to int.  y0 = t rounded down and y1 = b rounded up to a multiple
+ *                 of align_y, x0 / x1 likewise with align_x; h = y1 - y0, w = x1 - x0.  The ROI is the INTERSECTION with
+ *                 the picture: it is neither shifted nor padded, so at a border the crop loses the requested aspect and
+ *                 margin (ppn_ingest_rois stretches what is there to the output size).
+ *   7 degenerate  unless h >= min_size && w >= min_size: status = PPN_ROI_DEGENERATE and the ROI is (0, 0, 0, 0).  A box
+ *                 wholly outside the picture, a box too small, an inverted box, a NaN or an infinity anywhere land here.
+ *   8 otherwise   status = PPN_ROI_OK and the ROI is (y0, x0, h, w): inside the picture, aligned, at least min_size, and it
+ *                 contains the mapped box's part of the picture.
+ *
+ * Every slot of roi and status is written, rows of other frames or beyond max_rois are not.  One launch on `stream`, no
+ * allocation, no host synchronisation, no atomics: two runs give identical bytes.  PPN_E_INVALID before anything is launched
+ * for: a NULL pointer; K outside 1..PPN_MAX_KP; max_humans outside 1..1024; max_rois, frames or min_size < 1; src_h or src_w
+ * outside 1..16384; align_y / align_x not 1 or 2, or one that does not divide the picture's size; min_size below an
+ * alignment; an unknown mode; sy or sx not finite or not > 0; a margin that is NaN, negative or infinite; an aspect that is
+ * NaN, negative or infinite; a bbox or roi that is not 16-byte aligned.
+ */
+#define PPN_ROI_OK 0
+#define PPN_ROI_EMPTY 1          /* no person in the slot / an all-zero rectangle */
+#define PPN_ROI_DEGENERATE 2     /* a person whose rectangle is below min_size, outside the picture or not finite */
+#define PPN_ROI_BAD 4            /* ppn_ingest_rois: a rectangle that must not be read */
+#define PPN_ROI_MODE_ROOT 0
+#define PPN_ROI_MODE_PEOPLE 1
+typedef struct ppn_roi_cfg {
+    int32_t K, max_humans, max_rois;
+    int32_t src_h, src_w;          /* the picture the ROIs are cut from */
+    float sy, sx;                  /* box pixels -> source pixels */
+    int32_t mode;                  /* PPN_ROI_MODE_* */
+    float margin;                  /* added to each half size, as a fraction of it; default 0.1 */
+    float aspect;                  /* dst_w / dst_h, or 0: keep the box's shape */
+    int32_t align_y, align_x;      /* 1 or 2: NV12 / I420 need 2, 2; YUYV 1, 2; packed BGR 1, 1 */
+    int32_t min_size;
+} ppn_roi_cfg;
+int ppn_people_rois(const ppn_roi_cfg* cfg, const int32_t* count, const int32_t* kp_cell, const float* bbox, int32_t frames,
+                    int32_t* roi, int32_t* status, void* stream);
+
+/*
+ * ppn_ingest_rois (csrc/ingest.hip): the ROIs of F = d->batch raw frames into d->dst u8 [F * max_rois][dst_h][dst_w][3], one
+ * launch; `d` is read as ppn_ingest_windows reads it (all four formats), `roi` is a DEVICE table i32 [F][max_rois][4] of
+ * (y0, x0, h, w) and image f * max_rois + r is ROI r of frame f.  NORMATIVE: for a good ROI every output byte equals what
+ * ppn_ingest_windows writes for a layout of one window holding that rectangle -- the clamping of the taps at the ROI's
+ * borders, the exact-halving path chosen per ROI (h == 2 * dst_h && w == 2 * dst_w) beside bilinear ROIs of the same launch,
+ * the flip, dst_bgr and both store paths.  The per-axis scale is the double (double)w / (double)dst_w, divided on the device
+ * (an IEEE division: the host's bits).
+ *
+ * The table is data the host never sees, so it is judged on the device, per workgroup and before any tap:
+ *   (0, 0, 0, 0)   an empty slot: the image is all zero bytes and status |= PPN_ROI_EMPTY;
+ *   a bad ROI      (a negative origin; h < 1 or w < 1; a rectangle that leaves the picture; an odd x0 or w in a YUV format; an
+ *                  odd y0 or h in NV12 / I420): the image is all zero bytes and status |= PPN_ROI_BAD.
+ * Neither reads the source at all.  `status` i32 [F][max_rois] may be NULL; otherwise the bits are OR-ed into what it holds
+ * (the table ppn_people_rois wrote, or zeros), by one work item per image and without atomics.
+ *
+ * PPN_E_INVALID, before any launch: everything ppn_ingest_windows refuses of `d`; a NULL roi; max_rois < 1; F * max_rois
+ * above 65535.  Runs on `stream`, allocates nothing, does not synchronise.
+ */
+int ppn_ingest_rois(const ppn_ingest_desc* d, const int32_t* roi, int32_t max_rois, int32_t* status, void* stream);
+
+/*
  * Train-time augmentation on the device (aug.py:13-160: IAA + ToNormalizedTensor), csrc/augment.hip.  Coordinates are pixel
  * indices with pixel centres at integers.  Per image the HOST builds the forward map F (source point -> output point:
  * rotation + isotropic scale about ((w-1)/2, (h-1)/2), minus the crop's (left, top), centre-aligned resize

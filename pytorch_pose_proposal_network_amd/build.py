@@ -61,6 +61,9 @@ SOURCES = [
     # windows.hip is bit-exact with a NumPy restatement at the merge threshold and in the mapped boxes: y * sy + y0
     # uncontracted, the scales' and the IoU's divides IEEE-rounded
     ("windows.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
+    # crops.hip is bit-exact with a NumPy restatement in the rectangles it writes: hh + hh * margin uncontracted, the
+    # aspect's divide IEEE-rounded
+    ("crops.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
 ]
 
 

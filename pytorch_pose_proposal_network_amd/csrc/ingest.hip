@@ -272,6 +272,65 @@ ingest_windows_kernel(YuvSrc s, YuvCoeff k, WinArgs wa, unsigned char* __restric
                   wa.area2[i], dwords, oy, ox0);
 }
 
+// ---- regions of interest of raw frames (include/ppn.h: ppn_ingest_rois) ------------------------------------------------
+// Image f * max_rois + r is ROI r of frame f.  The rectangles are a table in device memory (ppn_people_rois writes it), read
+// per workgroup at a uniform address; nothing about it is known on the host, so the workgroup judges its rectangle before
+// any tap and the two scales are divided here.  An empty or bad slot gets zero bytes and never touches the source.
+template <int FMT>
+__global__ void __launch_bounds__(256)
+ingest_rois_kernel(YuvSrc s, YuvCoeff k, const int* __restrict__ roi, int* __restrict__ status, int max_rois, int Hs, int Ws,
+                   unsigned char* __restrict__ dst, int Hd, int Wd, int flip, int bgr, int dwords) {
+    const int ox0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const int oy = blockIdx.y * blockDim.y + threadIdx.y;
+    const int img = blockIdx.z;
+    const int* q = roi + (size_t)img * 4;
+    const int y0 = q[0], x0 = q[1], h = q[2], w = q[3];
+    int bits = 0;
+    if ((y0 | x0 | h | w) == 0) {
+        bits = PPN_ROI_EMPTY;
+    } else {
+        bool bad = y0 < 0 || x0 < 0 || h < 1 || w < 1 || h > Hs || w > Ws || y0 > Hs - h || x0 > Ws - w;
+        if (FMT != PPN_PIX_BGR24) bad = bad || ((x0 | w) & 1);
+        if (FMT == PPN_PIX_NV12 || FMT == PPN_PIX_I420) bad = bad || ((y0 | h) & 1);
+        if (bad) bits = PPN_ROI_BAD;
+    }
+    if (bits) {                                            // uniform: the whole workgroup leaves without a tap
+        if (status && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) status[img] |= bits;
+        if (ox0 >= Wd || oy >= Hd) return;
+        unsigned char* o = dst + (((size_t)img * Hd + oy) * Wd + ox0) * 3;
+        if (dwords) {
+            unsigned int* o4 = reinterpret_cast<unsigned int*>(o);
+            o4[0] = 0u;
+            o4[1] = 0u;
+            o4[2] = 0u;
+        } else {
+            const int n = min(4, Wd - ox0) * 3;
+            for (int j = 0; j < n; ++j) o[j] = 0;
+        }
+        return;
+    }
+    if (ox0 >= Wd || oy >= Hd) return;
+    const int f = img / max_rois;
+    const unsigned char* py = s.y + (long long)f * s.frame_stride + (long long)y0 * s.pitch;
+    const unsigned char *pu = nullptr, *pv = nullptr;
+    if (FMT == PPN_PIX_NV12) {
+        py += x0;
+        pu = s.u + (long long)f * s.frame_stride + (long long)(y0 >> 1) * s.pitch_c + x0;
+    } else if (FMT == PPN_PIX_I420) {
+        py += x0;
+        const long long o = (long long)f * s.frame_stride + (long long)(y0 >> 1) * s.pitch_c + (x0 >> 1);
+        pu = s.u + o;
+        pv = s.v + o;
+    } else if (FMT == PPN_PIX_YUYV) {
+        py += 2 * x0;
+    } else {
+        py += 3 * x0;
+    }
+    const int area2 = (h == 2 * Hd && w == 2 * Wd) ? 1 : 0;
+    yuv_quad<FMT>(py, pu, pv, s.pitch, s.pitch_c, k, dst, img, h, w, Hd, Wd, (double)w / (double)Wd, (double)h / (double)Hd,
+                  flip, bgr, area2, dwords, oy, ox0);
+}
+
 }  // namespace
 
 extern "C" int ppn_yuv_coefficients(int32_t matrix, int32_t full_range, int32_t out6[6]) {
@@ -393,3 +452,29 @@ extern "C" int ppn_ingest_windows(const ppn_ingest_desc* d, const ppn_window_lay
     return PPN_OK;
 }
 
+extern "C" int ppn_ingest_rois(const ppn_ingest_desc* d, const int32_t* roi, int32_t max_rois, int32_t* status,
+                               void* stream) {
+    static const char who[] = "ppn_ingest_rois";
+    if (const int rc = check_desc(who, d, true)) return rc;
+    if (!roi) return ppn::fail(PPN_E_INVALID, "%s: NULL roi table", who);
+    if (max_rois < 1) return ppn::fail(PPN_E_INVALID, "%s: max_rois %d below 1", who, max_rois);
+    if ((int64_t)d->batch * max_rois > 65535)
+        return ppn::fail(PPN_E_INVALID, "%s: %d frames x %d ROIs exceed 65535 images", who, d->batch, max_rois);
+    const int fmt = d->format;
+    const YuvCoeff k = coeff_of(d);
+    const YuvSrc s = planes_of(d);
+    const int dwords = (d->dst_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d->dst) & 3) == 0) ? 1 : 0;
+    const dim3 block(32, 8), grid((d->dst_w + 127) / 128, (d->dst_h + 7) / 8, d->batch * max_rois);
+    unsigned char* dst = static_cast<unsigned char*>(d->dst);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define PPN_ROI_LAUNCH(F)                                                                                               \
+    hipLaunchKernelGGL(ingest_rois_kernel<F>, grid, block, 0, st, s, k, roi, status, max_rois, d->src_h, d->src_w, dst, \
+                       d->dst_h, d->dst_w, d->flip ? 1 : 0, d->dst_bgr ? 1 : 0, dwords)
+    if (fmt == PPN_PIX_NV12) PPN_ROI_LAUNCH(PPN_PIX_NV12);
+    else if (fmt == PPN_PIX_I420) PPN_ROI_LAUNCH(PPN_PIX_I420);
+    else if (fmt == PPN_PIX_YUYV) PPN_ROI_LAUNCH(PPN_PIX_YUYV);
+    else PPN_ROI_LAUNCH(PPN_PIX_BGR24);
+#undef PPN_ROI_LAUNCH
+    PPN_LAUNCH_CHECK();
+    return PPN_OK;
+}

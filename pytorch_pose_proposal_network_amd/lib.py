@@ -22,6 +22,8 @@ PPN_PIX_NV12, PPN_PIX_I420, PPN_PIX_YUYV = 0, 1, 2                         # ppn
 PPN_PIX_BGR24 = 3                                                           # ppn_ingest_windows only
 PPN_MAX_WINDOWS, PPN_MERGE_MAX_CAND = 16, 512                               # ppn_merge_windows (csrc/windows.hip)
 PPN_MERGE_FLAG_CAND_OVERFLOW, PPN_MERGE_FLAG_OUT_OVERFLOW = 1, 2
+PPN_ROI_OK, PPN_ROI_EMPTY, PPN_ROI_DEGENERATE, PPN_ROI_BAD = 0, 1, 2, 4        # ppn_people_rois / ppn_ingest_rois status bits
+PPN_ROI_MODE_ROOT, PPN_ROI_MODE_PEOPLE = 0, 1                               # ppn_roi_cfg.mode (csrc/crops.hip)
 PPN_STEM_RAW_S2 = 1 << 16          # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
 
 
@@ -169,6 +171,13 @@ class MergeCfg(C.Structure):
     """ppn_merge_cfg (csrc/windows.hip)."""
     _fields_ = [(n, C.c_int32) for n in ("K", "inH", "inW", "max_humans", "max_out")] + [
         ("merge_thr", C.c_float), ("fuse", C.c_int32)]
+
+
+class RoiCfg(C.Structure):
+    """ppn_roi_cfg (csrc/crops.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("K", "max_humans", "max_rois", "src_h", "src_w")] + [
+        ("sy", C.c_float), ("sx", C.c_float), ("mode", C.c_int32), ("margin", C.c_float), ("aspect", C.c_float)] + [
+        (n, C.c_int32) for n in ("align_y", "align_x", "min_size")]
 
 
 class PPNError(RuntimeError):
@@ -325,6 +334,8 @@ _SIGNATURES.update({
     "ppn_ingest_windows": (C.c_int, [C.POINTER(IngestDesc), C.POINTER(WindowLayout), C.c_void_p]),
     "ppn_merge_windows": (C.c_int, [C.POINTER(MergeCfg), C.POINTER(WindowLayout)] + [C.c_void_p] * 4 + [C.c_int32] +
                           [C.c_void_p] * 6),
+    "ppn_people_rois": (C.c_int, [C.POINTER(RoiCfg)] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3),
+    "ppn_ingest_rois": (C.c_int, [C.POINTER(IngestDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
 })
 
 EXPORTS = tuple(_SIGNATURES)

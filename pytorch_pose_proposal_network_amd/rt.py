@@ -13,7 +13,8 @@ rt_test.inference does and ``inference_batch_drawn`` the drawn batch, both paint
 datatest.py:162-232).  ``inference_batch_tracked`` / ``inference_tracked`` add what the reference's loop lacks: ids that follow
 a person from frame to frame (track.py), again without reading the people lists back.  ``inference_windows`` runs a big raw
 frame as overlapping windows of the batch and joins the people in frame pixels on the device (windows.py);
-``inference_windows_drawn`` paints them straight onto the raw frames (render.Renderer.draw_yuv).
+``inference_windows_drawn`` paints them straight onto the raw frames (render.Renderer.draw_yuv); ``inference_crops`` cuts
+every detected person out of the raw frame as a fixed-size picture for a following model (crops.py).
 """
 from __future__ import annotations
 
@@ -331,6 +332,41 @@ def inference_windows_drawn(raw: torch.Tensor, fmt: str, src_hw, model: PoseProp
         renderer = R.Renderer(raw.shape[0], res.max_humans, raw.device)
     return res, renderer.draw_yuv(raw, fmt, src_hw, res, visbbox=visbbox, out=out, pitch=pitch, matrix=matrix,
                                   full_range=full_range)
+
+
+def inference_crops(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNet, cropper, layout=None, tracker=None,
+                    decoder: Optional[D.Decoder] = None, merger=None, detection_thresh: float = 0.15, size=384,
+                    matrix: str = "bt601", full_range: bool = False, pitch: Optional[int] = None, merge_thr: float = 0.3,
+                    fuse: bool = True):
+    """Detect the people of F raw frames and cut each of them out of the raw frame for a following model (crops.py), all on
+    the device: ingest -> forward -> fused decode (-> window merge when `layout`, a windows.WindowLayout of `src_hw`, is
+    given: ``inference_windows``) (-> `tracker`.update when given) -> rectangles -> crops.  `cropper` is a
+    crops.PersonCropper of F frames on `src_hw` / `fmt` whose ``coords_hw`` is the space the people come out in: the frame
+    with a layout, the network input (`size`) without.  Returns ``(DecodeResult, CropResult)``, with a tracker
+    ``(DecodeResult, CropResult, TrackResult)``: crop r, bbox r and ids r of a frame are the same person.  Pass a Decoder
+    (and a WindowMerger) to allocate nothing per call.  Nothing is read back."""
+    from . import windows as W
+    H, Wd = int(src_hw[0]), int(src_hw[1])
+    h, w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    space = (H, Wd) if layout is not None else (h, w)
+    if cropper.src_hw != (H, Wd) or cropper.fmt != fmt or cropper.coords_hw != space or cropper.frames != raw.shape[0]:
+        raise ValueError(f"the cropper cuts {cropper.frames} {cropper.fmt} frames of {cropper.src_hw} with boxes in "
+                         f"{cropper.coords_hw}; the call has {raw.shape[0]} {fmt} frames of {(H, Wd)} and people in {space}")
+    if layout is not None:
+        res = inference_windows(raw, fmt, src_hw, model, layout, decoder, merger, detection_thresh, size, False, matrix,
+                                full_range, pitch, merge_thr, fuse)
+    else:
+        frames = raw.shape[0]
+        buf = model.input_buffer(frames, h, w, True, True)
+        W.ingest_windows(raw, fmt, W.WindowLayout((H, Wd), [(0, 0, H, Wd)]), (h, w), buf, False, matrix, full_range, pitch)
+        unary, keys = model.forward_u8(buf, fused_decode=True)
+        if decoder is None:
+            decoder = D.Decoder(frames, (unary.shape[2], unary.shape[3]), (h, w), model.local_grid_size, detection_thresh,
+                                device=unary.device)
+        res = decoder.decode_fused(unary, keys)
+    tracks = tracker.update(res) if tracker is not None else None
+    out = cropper(raw, res, matrix=matrix, full_range=full_range, pitch=pitch)
+    return (res, out) if tracker is None else (res, out, tracks)
 
 
 def inference_tracked(image, model: PoseProposalNet, outsize, local_grid_size, tracker, detection_thresh: float = 0.15,

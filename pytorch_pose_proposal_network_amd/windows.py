@@ -11,9 +11,9 @@ windows are joined in frame pixels on the device, over csrc/ingest.hip (ppn_inge
                                               window images to frame pixels, drops the duplicates of the overlaps and fuses
                                               keypoints: one launch, no allocation, no host synchronisation, no D2H.
 
-The rules are include/ppn.h's; tests/windows_ref.py restates them in NumPy.  Not built: letterboxing, windows that differ
-per frame, more than 16 windows or 512 candidates per frame, InferencePipeline / MultiLaneInference integration,
-flip-averaging combined with windows.
+The rules are include/ppn.h's; tests/windows_ref.py restates them in NumPy.  Not built: letterboxing, more than 16 windows or
+512 candidates per frame, InferencePipeline / MultiLaneInference integration, flip-averaging combined with windows.
+Rectangles that differ per frame and come from the device are crops.py's (ppn_ingest_rois): a layout stays a host struct.
 """
 from __future__ import annotations
 
@@ -105,22 +105,18 @@ class WindowLayout:
         return cls((H, W), [(y, x, h, w) for y in ys for x in xs])
 
 
-def ingest_windows(raw: torch.Tensor, fmt: str, layout: WindowLayout, size=384, out: Optional[torch.Tensor] = None,
-                   flip: bool = False, matrix: str = "bt601", full_range: bool = False,
-                   pitch: Optional[int] = None) -> torch.Tensor:
-    """The windows of raw video frames -> u8 RGB [F * n, h, w, 3] in one launch (ppn_ingest_windows): every image is what
-    ``rt.ingest_yuv`` gives on the window's own crop of the planes.  `raw`: u8 CUDA tensor [F, nbytes] laid out as
-    ``rt.yuv_frame_layout(fmt, layout.src_hw, pitch)`` says (`fmt` "nv12", "i420" or "yuyv"), or for `fmt` "bgr" packed
-    BGR frames [F, H, pitch] with pitch >= 3 * W bytes per row (a [F, H, W, 3] tensor is taken as it is).  `out` may be
-    ``model.input_buffer(F * n, h, w, ...)``."""
+def _raw_planes(who: str, raw: torch.Tensor, fmt: str, src_hw, matrix: str, pitch: Optional[int]):
+    """What ``ingest_windows`` and ``crops.ingest_rois`` share: the checks of the raw frames and the plane fields of the
+    ppn_ingest_desc.  Returns (raw, planes): `raw` as it is read (made contiguous where its rows are not), `planes` the
+    descriptor's pitch, pitch_c, frame_stride, y, u, v."""
     from . import rt
     if fmt not in _PIX_FORMATS:
         raise ValueError(f"fmt must be one of {sorted(_PIX_FORMATS)}, not {fmt!r}")
     if matrix not in _YUV_MATRICES:
         raise ValueError(f"matrix must be one of {sorted(_YUV_MATRICES)}, not {matrix!r}")
     if not (isinstance(raw, torch.Tensor) and raw.is_cuda and raw.dtype == torch.uint8):
-        raise ValueError("ingest_windows expects a uint8 CUDA tensor")
-    H, W = layout.src_hw
+        raise ValueError(f"{who} expects a uint8 CUDA tensor")
+    H, W = int(src_hw[0]), int(src_hw[1])
     base = raw.data_ptr()
     if fmt == "bgr":
         if raw.dim() == 4 and tuple(raw.shape[1:]) == (H, W, 3):
@@ -145,6 +141,19 @@ def ingest_windows(raw: torch.Tensor, fmt: str, layout: WindowLayout, size=384, 
             raise ValueError(f"a {fmt} frame of {(H, W)} with pitch {pitch} has {nbytes} bytes, raw rows have {raw.shape[1]}")
         planes = dict(pitch=pitch, pitch_c=pitch_c, frame_stride=raw.stride(0) if raw.shape[0] > 1 else raw.shape[1], y=base,
                       u=None if u_off is None else base + u_off, v=None if v_off is None else base + v_off)
+    return raw, planes
+
+
+def ingest_windows(raw: torch.Tensor, fmt: str, layout: WindowLayout, size=384, out: Optional[torch.Tensor] = None,
+                   flip: bool = False, matrix: str = "bt601", full_range: bool = False,
+                   pitch: Optional[int] = None) -> torch.Tensor:
+    """The windows of raw video frames -> u8 RGB [F * n, h, w, 3] in one launch (ppn_ingest_windows): every image is what
+    ``rt.ingest_yuv`` gives on the window's own crop of the planes.  `raw`: u8 CUDA tensor [F, nbytes] laid out as
+    ``rt.yuv_frame_layout(fmt, layout.src_hw, pitch)`` says (`fmt` "nv12", "i420" or "yuyv"), or for `fmt` "bgr" packed
+    BGR frames [F, H, pitch] with pitch >= 3 * W bytes per row (a [F, H, W, 3] tensor is taken as it is).  `out` may be
+    ``model.input_buffer(F * n, h, w, ...)``."""
+    raw, planes = _raw_planes("ingest_windows", raw, fmt, layout.src_hw, matrix, pitch)
+    H, W = layout.src_hw
     h, w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
     b = raw.shape[0] * layout.n
     if out is None:
