@@ -842,6 +842,114 @@ int ppn_draw_humans_yuv(const ppn_draw_cfg* cfg, const ppn_yuv_surface* src, con
                         void* stream);
 
 /*
+ * Redaction (no counterpart in the reference; csrc/redact.hip): the detected people -- by default their heads -- made
+ * unrecognisable in the RAW frame before it leaves the box, in the format the encoder takes, without an RGB round trip and
+ * without a host synchronisation.  Two launches: ppn_redact_cells turns people lists and a small hold state into per-frame
+ * bit masks over a grid of square cells, ppn_redact_yuv applies a mask to raw surfaces.  tests/redact_ref.py restates both
+ * in NumPy; kernels and restatement agree on every byte.  Not built: blur, ellipses, a per-track hold that follows a moving
+ * person, MultiLaneInference integration.  No claim is made about how well the neck + top boxes cover a face: the
+ * synthetic checkpoints say nothing about that.
+ *
+ * The cell grid.  Cells are cell x cell luma pixels, cell in {8, 16, 32}.  A src_h x src_w picture has CH = ceil(src_h / cell)
+ * rows and CW = ceil(src_w / cell) columns of cells; those of the last row or column may be partial.  A frame's mask is
+ * u32 [CH][MW], MW = ceil(CW / 32): cell (cy, cx) is bit cx & 31 of word [cy][cx >> 5].  A reader ignores the bits at and
+ * above CW of a row's last word.  cell is even, so a cell's pixels own whole chroma groups in every format.
+ *
+ * ppn_redact_cells: a decode result (count, kp_cell, bbox as ppn_people_rois takes them) -> mask and flags.  Image
+ * b = s * frames + t is frame t of stream s (the tracker's layout); streams are independent, the frames of a stream are
+ * taken in ascending t within a call and from call to call.  Every f32 step is one IEEE operation rounded on its own.
+ *
+ * Person p of image b takes part when p < min(max(count[b], 0), max_humans) and kp_cell[b][p][0] >= 0.  Then:
+ *   1 set      the keypoints j < K with bit j of kp_mask set and kp_cell[b][p][j] >= 0.  If there are none:
+ *              PPN_REDACT_FALLBACK_PERSON takes all present keypoints j < K (the root is one, so the set is not empty:
+ *              better to hide too much than to show a face); PPN_REDACT_FALLBACK_NONE: the person contributes nothing.
+ *   2 box      the union of the set's boxes in ascending j: the first box, then per further box the smaller ymin / xmin
+ *              (v < b ? v : b) and the larger ymax / xmax (v > b ? v : b).  If a number of a box of the set is not finite,
+ *              the person contributes nothing and PPN_REDACT_FLAG_BAD_BOX is set.  Boxes outside the set do not count, whatever
+ *              they hold.
+ *   3 mapping  ppn_people_rois' rules 3 and 4, operation for operation, without the aspect rule: Y = y * sy, X = x * sx;
+ *              cy = (ymin + ymax) * 0.5f; hh = (ymax - ymin) * 0.5f; hh = hh + hh * margin; cx and hw likewise.
+ *   4 edges    t = floorf(cy - hh), b = ceilf(cy + hh), l = floorf(cx - hw), r = ceilf(cx + hw).  If one of the four is
+ *              not finite: nothing, and BAD_BOX.  Each is limited as a float, fminf(fmaxf(v, 0), (float)src_h) for rows,
+ *              src_w for columns, and converted to int.  t >= b or l >= r: nothing (a box outside the picture or an
+ *              inverted box is no error).
+ *   5 cells    the person covers the cell rows t / cell .. (b - 1) / cell and columns l / cell .. (r - 1) / cell
+ *              (integer divisions; both ends included).
+ * covered(c) is the OR over the image's people.  flags[b] = PPN_REDACT_FLAG_BAD_BOX if any person of image b set it, else
+ * 0: written, not accumulated.
+ *
+ * Hold.  ttl u8 [streams][CH][CW] holds one byte per cell and stream; all zero is a fresh state and zeroing it is the reset.
+ * Per frame and cell: ttl' = covered ? hold + 1 : (ttl > 0 ? ttl - 1 : 0), and the cell's mask bit is ttl' > 0 -- a cell
+ * stays masked for `hold` more frames after the last frame that covered it.  With hold == 0 the mask is `covered` and ttl
+ * is neither read nor written (it may be NULL).  A cell's history depends on no other cell.
+ *
+ * Every word of mask [streams * frames][CH][MW] and of flags [streams * frames] is written, bits at and above CW as 0;
+ * with hold > 0 every byte of ttl is.  One launch on `stream`, no atomics, no allocation, no host synchronisation: the call
+ * can be captured into a graph and two runs from the same state give identical bytes.  PPN_E_INVALID before any launch
+ * for: a NULL pointer (ttl may be NULL iff hold == 0); K outside 1..PPN_MAX_KP; max_humans outside 1..1024; streams or
+ * frames < 1 (or streams above 65535); src_h or src_w outside 1..16384; cell not 8, 16 or 32; sy or sx not finite or not
+ * > 0; a margin that is NaN, negative or infinite; hold outside 0..254; an unknown fallback; a kp_mask without a bit below
+ * K; a bbox that is not 16-byte aligned.
+ */
+#define PPN_REDACT_FALLBACK_PERSON 0
+#define PPN_REDACT_FALLBACK_NONE 1
+#define PPN_REDACT_FLAG_BAD_BOX 1
+typedef struct ppn_redact_cells_cfg {
+    int32_t K, max_humans;
+    int32_t src_h, src_w, cell;
+    float sy, sx;            /* box pixels -> source pixels, as ppn_roi_cfg */
+    uint32_t kp_mask;        /* bit j: keypoint j belongs to the region (default: neck | top = the head) */
+    int32_t fallback;        /* PPN_REDACT_FALLBACK_PERSON (default) | PPN_REDACT_FALLBACK_NONE */
+    float margin;            /* as ppn_roi_cfg.margin; default 0.25 */
+    int32_t hold;            /* 0..254 frames a cell stays masked after it was last covered */
+} ppn_redact_cells_cfg;
+int ppn_redact_cells(const ppn_redact_cells_cfg* cfg, uint8_t* ttl, const int32_t* count, const int32_t* kp_cell,
+                     const float* bbox, int32_t streams, int32_t frames, uint32_t* mask, int32_t* flags, void* stream);
+
+/*
+ * ppn_redact_yuv: masks u32 [batch][CH][MW] (device; CH, CW, MW from the surface's height and width and cfg->cell) ->
+ * redacted surfaces.  The surfaces are ppn_draw_humans_yuv's (NV12, I420, YUYV: any pitch and alignment, frame_stride);
+ * this entry also takes PPN_PIX_BGR24 as ppn_ingest_windows does: y = the packed B, G, R bytes, pitch >= 3 * width, the
+ * size may be odd, u, v, pitch_c, matrix and full_range are not read.
+ *
+ * A masked cell (cy, cx) owns these sample sets, every one clipped to the picture:
+ *   luma              the pixels (y, x), y in [cy * cell, min((cy + 1) * cell, height)), x likewise with width
+ *   NV12 / I420       U and V each on their own: the chroma samples (i, j), i in [cy * cell / 2, min((cy + 1) * cell / 2,
+ *                     height / 2)), j in [cx * cell / 2, min((cx + 1) * cell / 2, width / 2))
+ *   YUYV              U and V each on their own: rows as luma, j in [cx * cell / 2, min((cx + 1) * cell / 2, width / 2))
+ *   BGR24             the three channels each on their own, over the luma set
+ * PPN_REDACT_MOSAIC: every sample of a set becomes the set's rounded mean (s + (n >> 1)) / n, s the sum and n the number
+ * of the set's samples INSIDE the picture (not cell * cell at a border), an integer division.  The sums stay below
+ * 1024 * 255, and integer sums give the same bytes in any order.  The mean of equal values is that value: redacting a
+ * redacted frame again with the same mask changes nothing.  PPN_REDACT_FILL: every sample of a set takes its plane's byte
+ * of cfg->fill: fill[0] luma, fill[1] U, fill[2] V (ppn_rgb_to_yuv converts a colour); BGR24: fill[0..2] in memory order.
+ * Samples of unmasked cells keep their bytes.  Mask bits at and above CW are ignored.
+ *
+ * dst == src in every plane and in pitch, pitch_c and frame_stride: in place; only samples of masked cells are stored, and
+ * a cell is read completely before any of it is written, by the one wave that owns it.  Otherwise out of place: no dst
+ * plane may be a src plane (nor overlap one), every content byte of every dst plane is written (unmasked samples are
+ * copied) and the bytes between a row's content and its pitch never are.  The kernel moves dwords (a row's
+ * last 1..3 bytes of a cell at the picture's border as bytes) when every plane pointer, pitch, pitch_c and frame_stride of
+ * both surfaces is a multiple of 4, bytes otherwise -- the same bytes.
+ *
+ * One launch on `stream`, no allocation, no host synchronisation, no atomics.  PPN_E_INVALID before any launch: everything
+ * ppn_draw_humans_yuv refuses of a surface pair, except that PPN_PIX_BGR24 is accepted (a NULL surface or required plane,
+ * an unknown format, an unknown matrix of a YUV surface, an odd width or an odd NV12 / I420 height, a pitch or frame_stride
+ * below the content, surfaces that differ in format or size -- for YUV also in matrix or range --, a shared plane without
+ * everything shared); a NULL cfg or mask; cell not 8, 16 or 32; an unknown mode; batch < 1 or above 65535; height or width
+ * above 16384.
+ */
+#define PPN_REDACT_MOSAIC 0
+#define PPN_REDACT_FILL 1
+typedef struct ppn_redact_cfg {
+    int32_t cell;            /* 8, 16, 32: the mask's grid */
+    int32_t mode;            /* PPN_REDACT_MOSAIC | PPN_REDACT_FILL */
+    uint8_t fill[4];         /* FILL: Y, U, V (BGR24: the three bytes in memory order), unused */
+} ppn_redact_cfg;
+int ppn_redact_yuv(const ppn_redact_cfg* cfg, const ppn_yuv_surface* src, const ppn_yuv_surface* dst, int32_t batch,
+                   const uint32_t* mask, void* stream);
+
+/*
  * The per-image matching of a validation epoch on the device (main.py:1017-1172 validate / 886-1014 test_output ->
  * datatest.evaluation -> eval_helpers.assignGTmulti, eval_helpers.py:300-468), csrc/validate.hip: one batch of compact
  * people lists against the resident ground truth of the whole validation set, one workgroup per image, emitting the

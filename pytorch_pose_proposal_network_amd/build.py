@@ -64,6 +64,9 @@ SOURCES = [
     # crops.hip is bit-exact with a NumPy restatement in the rectangles it writes: hh + hh * margin uncontracted, the
     # aspect's divide IEEE-rounded
     ("crops.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
+    # redact.hip is bit-exact with a NumPy restatement in the cells a person covers: crops.hip's hh + hh * margin, uncontracted
+    # (no MFMA code, hence no NOSLP)
+    ("redact.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
 ]
 
 

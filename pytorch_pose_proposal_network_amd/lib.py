@@ -24,6 +24,8 @@ PPN_MAX_WINDOWS, PPN_MERGE_MAX_CAND = 16, 512                               # pp
 PPN_MERGE_FLAG_CAND_OVERFLOW, PPN_MERGE_FLAG_OUT_OVERFLOW = 1, 2
 PPN_ROI_OK, PPN_ROI_EMPTY, PPN_ROI_DEGENERATE, PPN_ROI_BAD = 0, 1, 2, 4        # ppn_people_rois / ppn_ingest_rois status bits
 PPN_ROI_MODE_ROOT, PPN_ROI_MODE_PEOPLE = 0, 1                               # ppn_roi_cfg.mode (csrc/crops.hip)
+PPN_REDACT_FALLBACK_PERSON, PPN_REDACT_FALLBACK_NONE, PPN_REDACT_FLAG_BAD_BOX = 0, 1, 1   # ppn_redact_cells (csrc/redact.hip)
+PPN_REDACT_MOSAIC, PPN_REDACT_FILL = 0, 1                                   # ppn_redact_cfg.mode
 PPN_STEM_RAW_S2 = 1 << 16          # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
 
 
@@ -178,6 +180,18 @@ class RoiCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("K", "max_humans", "max_rois", "src_h", "src_w")] + [
         ("sy", C.c_float), ("sx", C.c_float), ("mode", C.c_int32), ("margin", C.c_float), ("aspect", C.c_float)] + [
         (n, C.c_int32) for n in ("align_y", "align_x", "min_size")]
+
+
+class RedactCellsCfg(C.Structure):
+    """ppn_redact_cells_cfg (csrc/redact.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("K", "max_humans", "src_h", "src_w", "cell")] + [
+        ("sy", C.c_float), ("sx", C.c_float), ("kp_mask", C.c_uint32), ("fallback", C.c_int32), ("margin", C.c_float),
+        ("hold", C.c_int32)]
+
+
+class RedactCfg(C.Structure):
+    """ppn_redact_cfg (csrc/redact.hip)."""
+    _fields_ = [("cell", C.c_int32), ("mode", C.c_int32), ("fill", C.c_uint8 * 4)]
 
 
 class PPNError(RuntimeError):
@@ -336,6 +350,9 @@ _SIGNATURES.update({
                           [C.c_void_p] * 6),
     "ppn_people_rois": (C.c_int, [C.POINTER(RoiCfg)] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3),
     "ppn_ingest_rois": (C.c_int, [C.POINTER(IngestDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ppn_redact_cells": (C.c_int, [C.POINTER(RedactCellsCfg)] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    "ppn_redact_yuv": (C.c_int, [C.POINTER(RedactCfg), C.POINTER(YuvSurface), C.POINTER(YuvSurface), C.c_int32, C.c_void_p,
+                                 C.c_void_p]),
 })
 
 EXPORTS = tuple(_SIGNATURES)
