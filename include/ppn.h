@@ -1082,6 +1082,84 @@ int ppn_track_update(const ppn_track_cfg* cfg, const ppn_track_state* st, const 
                      float* out_xy /* or NULL */, int32_t* out_live, void* stream);
 
 /*
+ * Per-track skeleton clips on the device (no counterpart in the reference), csrc/clips.hip: the last T = cfg->length frames
+ * of every tracked person's keypoints, kept as a ring per track id in up to PPN_CLIP_SLOTS resident clips per stream and
+ * handed out as one f32 [3][T][K] tensor (planes x, y, score) per clip: what a skeleton-based action model takes.
+ * ppn_clip_push consumes ppn_decode's people lists and ppn_track_update's out_id (and, if wanted, its out_xy);
+ * ppn_clip_gather writes all clips of all streams.  tests/clips_ref.py restates the rules below in NumPy; kernels and
+ * restatement agree on bytes.
+ *
+ * ppn_clip_push.  Batch layout and n_frames are ppn_track_update's: image b = s * frames + t is frame t of stream s, only
+ * t < n_frames[s] is processed (a negative n_frames[s] counts as 0, NULL means `frames` each), the frames of a stream go in
+ * ascending t within the call, and a stream without a processed frame keeps every state byte and its flags word.  out_row
+ * i32 [B][max_humans] is fully written on every call, -1 in every entry of an image that is not processed.
+ * One processed frame, with P = min(max(count[b], 0), max_humans) and r = pos[s]:
+ *   a who takes part  person p < P takes part iff ids[b][p] > 0.  Keypoint k is present iff kp_cell[b][p][k] >= 0; a present
+ *                     keypoint's values are x, y = xy[b][p][k] when xy is given (ppn_track_update's out_xy, smoothed),
+ *                     otherwise the centre of its box, x = (box[1] + box[3]) * 0.5f, y = (box[0] + box[2]) * 0.5f, and
+ *                     score = score[b][p][k].  An absent keypoint contributes (0, 0, 0) whatever the inputs hold there.
+ *   b seen            a live slot (id != 0) whose id equals a participant's id: ring row r gets the person's three planes,
+ *                     mask row r its presence bits, ref the person's root box bbox[b][p][0]; gap = 0, len = min(len + 1, T).
+ *   c unseen          every other live slot: ring row r becomes all zero floats, mask row r 0; gap += 1,
+ *                     len = min(len + 1, T); when gap > max_gap the slot is freed: id = gap = len = 0 (ref, mask and ring
+ *                     keep their bytes: len guards them).  This is ppn_track_update's ageing rule: fed by a tracker with
+ *                     max_age == max_gap, both reset together, the live ids after every frame are the tracker's.
+ *   d births          the participants whose id no live slot holds, in ascending p, take the free slots in ascending index
+ *                     (slots freed in step c included): id, gap = 0, len = 1, ref and row r as in step b.  Without a free
+ *                     slot the person's out_row is -1 and PPN_CLIP_FLAG_SLOT_OVERFLOW is set.
+ *   e outputs         out_row[b][p] = the person's slot, -1 for non-participants, overflow and rows >= P; then
+ *                     pos[s] = (r + 1) % T.
+ * Precondition: the positive ids of one image are distinct (the tracker's are); otherwise the result is unspecified, but no
+ * access leaves the buffers.
+ *
+ * ppn_clip_gather.  Every byte of out f32 [S][64][3][T][K], out_id and out_len i32 [S][64] is written.  For slot (s, i):
+ * out_id and out_len are the state's id and len; time step j of the output is ring row (pos[s] + j) % T and is valid iff the
+ * slot is live and j >= T - len: the clip is chronological, its newest frame at j = T - 1, zero-padded on the left; invalid
+ * steps and free slots are zeros.  PPN_CLIP_NORM_NONE copies the valid rows.  PPN_CLIP_NORM_ROOT takes, from the slot's ref,
+ * cx = (ref[1] + ref[3]) * 0.5f, cy = (ref[0] + ref[2]) * 0.5f, h = ref[2] - ref[0], w = ref[3] - ref[1], s = h if h > w else
+ * w, replaced by 1.0f unless s > 0 (a degenerate or inverted box, a NaN); a present keypoint becomes ((x - cx) / s,
+ * (y - cy) / s, score), the subtraction and the IEEE division each rounded on its own, an absent one stays (0, 0, 0).  The
+ * reference box is the newest SEEN root box of the clip, not each frame's own: motion inside the clip survives.
+ *
+ * Each entry point is one launch on `stream` (push: one workgroup per stream; gather: one per slot), no allocation, no host
+ * synchronisation, no D2H: both can be captured into a graph.  No atomics -- each stream's workgroup owns its flags word,
+ * which it ORs into and the caller clears; two runs give identical bytes.  PPN_E_INVALID before anything is launched for:
+ * a NULL cfg, st, state pointer, input or output (only xy and n_frames may be NULL); K outside 1..PPN_MAX_KP; length outside
+ * 1..PPN_CLIP_MAX_LEN; max_gap < 0; an unknown norm; streams, frames or max_humans < 1.  PPN_E_UNSUPPORTED: max_humans >
+ * PPN_MATCH_MAX_PEOPLE.
+ */
+#define PPN_CLIP_SLOTS 64             /* clips per stream: as many as the tracker has tracks */
+#define PPN_CLIP_MAX_LEN 256
+#define PPN_CLIP_NORM_NONE 0
+#define PPN_CLIP_NORM_ROOT 1
+#define PPN_CLIP_FLAG_SLOT_OVERFLOW 1
+
+typedef struct ppn_clip_cfg {
+    int32_t K;        /* keypoints, keypoint 0 = the instance (root) box      */
+    int32_t length;   /* T: frames per clip, 1..PPN_CLIP_MAX_LEN               */
+    int32_t max_gap;  /* >= 0: frames a clip survives without its id           */
+    int32_t norm;     /* PPN_CLIP_NORM_*: what ppn_clip_gather does to x and y */
+} ppn_clip_cfg;
+
+typedef struct ppn_clip_state {       /* device pointers; ALL ZERO BYTES = fresh */
+    int32_t* id;      /* [S][64]        0 = free                                      */
+    int32_t* gap;     /* [S][64]        frames since the id was last seen             */
+    int32_t* len;     /* [S][64]        rows pushed since the slot was taken, <= T     */
+    float* ref;       /* [S][64][4]     root box (ymin,xmin,ymax,xmax) of the newest SEEN frame */
+    uint32_t* mask;   /* [S][64][T]     per ring row: bit k = keypoint k present; 0 = unseen frame */
+    float* ring;      /* [S][64][T][3][K]  planes x, y, score                          */
+    int32_t* pos;     /* [S]            the ring row the NEXT processed frame writes, 0..T-1 */
+    int32_t* flags;   /* [S]            OR of PPN_CLIP_FLAG_*, cleared by the caller   */
+} ppn_clip_state;
+
+int ppn_clip_push(const ppn_clip_cfg* cfg, const ppn_clip_state* st, const int32_t* count, const int32_t* kp_cell,
+                  const float* bbox, const float* score, const int32_t* ids, const float* xy /* or NULL */, int32_t streams,
+                  int32_t frames, int32_t max_humans, const int32_t* n_frames /* [S] or NULL = `frames` each */,
+                  int32_t* out_row /* [B][max_humans] */, void* stream);
+int ppn_clip_gather(const ppn_clip_cfg* cfg, const ppn_clip_state* st, int32_t streams, float* out /* [S][64][3][T][K] */,
+                    int32_t* out_id /* [S][64] */, int32_t* out_len /* [S][64] */, void* stream);
+
+/*
  * Horizontal-flip test-time averaging (no counterpart in the reference), csrc/tta.hip: the network sees a frame and its
  * left-right mirror image, the second head is mapped back and averaged with the first, and only then the decode runs.
  * Geometry as in ppn_decode_cfg; the heads are f32 [batch, C, H, W] NCHW with C = 6K + E*sH*sW: six unary groups resp, conf,

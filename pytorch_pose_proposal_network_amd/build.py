@@ -67,6 +67,9 @@ SOURCES = [
     # redact.hip is bit-exact with a NumPy restatement in the cells a person covers: crops.hip's hh + hh * margin, uncontracted
     # (no MFMA code, hence no NOSLP)
     ("redact.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
+    # clips.hip is bit-exact with a NumPy restatement in the normalised clips: (x - cx) / s as one subtraction and one
+    # IEEE-rounded divide
+    ("clips.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
 ]
 
 

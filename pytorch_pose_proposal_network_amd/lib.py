@@ -18,6 +18,8 @@ PPN_MATCH_JOINTS, PPN_MATCH_MAX_GT, PPN_MATCH_MAX_PEOPLE = 17, 64, 1024     # pp
 PPN_MATCH_FLAG_INDEX, PPN_MATCH_FLAG_GT_COUNT = 1, 2
 PPN_TRACK_SLOTS, PPN_TRACK_MAX_DET = 64, 256                                # ppn_track_update (csrc/track.hip)
 PPN_TRACK_FLAG_DET_OVERFLOW, PPN_TRACK_FLAG_SLOT_OVERFLOW = 1, 2
+PPN_CLIP_SLOTS, PPN_CLIP_MAX_LEN = 64, 256                                  # ppn_clip_push / ppn_clip_gather (csrc/clips.hip)
+PPN_CLIP_NORM_NONE, PPN_CLIP_NORM_ROOT, PPN_CLIP_FLAG_SLOT_OVERFLOW = 0, 1, 1
 PPN_PIX_NV12, PPN_PIX_I420, PPN_PIX_YUYV = 0, 1, 2                         # ppn_ingest_desc.format (csrc/ingest.hip)
 PPN_PIX_BGR24 = 3                                                           # ppn_ingest_windows only
 PPN_MAX_WINDOWS, PPN_MERGE_MAX_CAND = 16, 512                               # ppn_merge_windows (csrc/windows.hip)
@@ -149,6 +151,16 @@ class TrackCfg(C.Structure):
 class TrackState(C.Structure):
     """ppn_track_state: device pointers."""
     _fields_ = [(n, C.c_void_p) for n in ("id", "miss", "hits", "mask", "root", "xy", "last_id", "flags")]
+
+
+class ClipCfg(C.Structure):
+    """ppn_clip_cfg (csrc/clips.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("K", "length", "max_gap", "norm")]
+
+
+class ClipState(C.Structure):
+    """ppn_clip_state: device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in ("id", "gap", "len", "ref", "mask", "ring", "pos", "flags")]
 
 
 class IngestDesc(C.Structure):
@@ -345,6 +357,9 @@ _SIGNATURES.update({
     "ppn_tta_stage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "ppn_track_update": (C.c_int, [C.POINTER(TrackCfg), C.POINTER(TrackState)] + [C.c_void_p] * 4 + [C.c_int32] * 3 +
                          [C.c_void_p] * 6),
+    "ppn_clip_push": (C.c_int, [C.POINTER(ClipCfg), C.POINTER(ClipState)] + [C.c_void_p] * 6 + [C.c_int32] * 3 +
+                      [C.c_void_p] * 3),
+    "ppn_clip_gather": (C.c_int, [C.POINTER(ClipCfg), C.POINTER(ClipState), C.c_int32] + [C.c_void_p] * 4),
     "ppn_ingest_windows": (C.c_int, [C.POINTER(IngestDesc), C.POINTER(WindowLayout), C.c_void_p]),
     "ppn_merge_windows": (C.c_int, [C.POINTER(MergeCfg), C.POINTER(WindowLayout)] + [C.c_void_p] * 4 + [C.c_int32] +
                           [C.c_void_p] * 6),

@@ -280,6 +280,18 @@ def inference_batch_tracked(frames_u8: torch.Tensor, model: PoseProposalNet, tra
     return res, tracker.update(res)
 
 
+def inference_batch_clips(frames_u8: torch.Tensor, model: PoseProposalNet, tracker, clips, decoder: Optional[D.Decoder] = None,
+                          detection_thresh: float = 0.15, flip_tta: bool = False, merger=None, gather: bool = True):
+    """inference_batch_tracked plus the skeleton clips, all on the device: -> (DecodeResult, track.TrackResult,
+    clips.ClipRows, clips.ClipBatch or None).  `clips` is a clips.PoseClips of the tracker's streams, frames and max_humans
+    (give it max_gap = the tracker's max_age and reset the two together: then every live track has its clip); it takes the
+    tracker's smoothed centres.  ``gather=False`` only pushes the frames -- gather when the action model is due.  Nothing is
+    read back."""
+    res, tracks = inference_batch_tracked(frames_u8, model, tracker, decoder, detection_thresh, flip_tta, merger)
+    rows = clips.push(res, tracks)
+    return res, tracks, rows, clips.gather() if gather else None
+
+
 def inference_windows(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNet, layout, decoder: Optional[D.Decoder] = None,
                       merger=None, detection_thresh: float = 0.15, size=384, flip: bool = False, matrix: str = "bt601",
                       full_range: bool = False, pitch: Optional[int] = None, merge_thr: float = 0.3,
