@@ -1160,6 +1160,103 @@ int ppn_clip_gather(const ppn_clip_cfg* cfg, const ppn_clip_state* st, int32_t s
                     int32_t* out_id /* [S][64] */, int32_t* out_len /* [S][64] */, void* stream);
 
 /*
+ * Zones and counting lines on the device (no counterpart in the reference), csrc/zones.hip: how many people stand in a
+ * polygon, who entered or left it, how long they have been there, and how many crossed a line segment in which direction.
+ * ppn_zone_update consumes ppn_decode's people lists and ppn_track_update's out_id (and, if wanted, its out_xy), keeps up to
+ * PPN_ZONE_SLOTS tracked ids per stream and writes per-frame and per-person outputs.  tests/zones_ref.py restates the rules
+ * below in NumPy; kernel and restatement agree on bytes.
+ *
+ * Geometry is per stream (cameras differ), in the pixels of the people lists the call is given: zone z < zone_n[s] is the
+ * polygon of zone_nv[s][z] vertices zone_xy[s][z][i] = (x, y), line l < line_n[s] the directed segment from A = (ax, ay) to
+ * B = (bx, by) = line_xy[s][l].  The host validates the tables; the kernel clamps zone_n and line_n to 0..16 and a vertex
+ * number to 0..8, so it never reads outside a table, and treats a zone of fewer than 3 vertices as empty.  The bits z >=
+ * zone_n of `inside` and the words z >= zone_n of `dwell` are only ever cleared: reset a stream when its geometry changes.
+ *
+ * Batch layout and n_frames are ppn_track_update's: image b = s * frames + t is frame t of stream s, only t < n_frames[s] is
+ * processed (a negative n_frames[s] counts as 0, NULL means `frames` each), the frames of a stream go in ascending t within
+ * the call, and a stream without a processed frame keeps every state byte.  Every f32 step below is rounded on its own (no
+ * contraction, IEEE division).  One processed frame, with P = min(max(count[b], 0), max_humans):
+ *   a anchors   for person p < P the root box is bbox[b][p][0] = (ymin, xmin, ymax, xmax); ax = (xmin + xmax) * 0.5f; ay =
+ *               (ymin + ymax) * 0.5f for PPN_ZONE_ANCHOR_CENTER, ymax for PPN_ZONE_ANCHOR_BOTTOM; with xy given (ppn_track_update's
+ *               out_xy, smoothed) and anchor CENTER, (ax, ay) = xy[b][p][0].  The person is valid iff kp_cell[b][p][0] >= 0 and
+ *               ax and ay are finite.  in_now[p] has bit z set iff the person is valid and the even-odd ray test puts the
+ *               anchor into zone z: over the edges (i, j = i - 1 cyclic) toggle when (yi > ay) != (yj > ay) and
+ *               ax < (xj - xi) * (ay - yi) / (yj - yi) + xi.
+ *   b match     ppn_clip_push's steps a to d with `gap` and `max_gap`: the valid people with ids[b][p] > 0 take part, in
+ *               ascending p; a participant continues the live slot (id != 0) that holds its id (the first p wins the slot's
+ *               frame): the slot is SEEN, gap = 0; every other live slot is UNSEEN: gap += 1, and it is FREED when gap >
+ *               max_gap; then the participants whose id no live slot held, in ascending p, take the free slots in ascending
+ *               index (slots freed in this frame included): the slot is BORN, id = the id, gap = 0; without a free slot
+ *               PPN_ZONE_FLAG_SLOT_OVERFLOW is set.
+ *   c seen      with P0 = last, P1 = the person's anchor, in = inside: for every line l, side(P) = ((bx - ax_l) * (P.y - ay_l) -
+ *               (by - ay_l) * (P.x - ax_l)) >= 0; if side(P0) != side(P1), e0 = cross(P1 - P0, A - P0), e1 = cross(P1 - P0,
+ *               B - P0) with cross(u, v) = u.x * v.y - u.y * v.x, and the step crosses the segment iff (e0 <= 0 && e1 >= 0) ||
+ *               (e0 >= 0 && e1 <= 0): forward if side(P1), backward otherwise; line_total and the frame's out_line count it.
+ *               Zones z < zone_n: entered = in_now & ~in, exited = in & ~in_now; dwell[z] = dwell[z] + 1 (saturating at
+ *               2^31 - 1) if the bit stays set, 1 if newly set, 0 if clear.  Then last = P1, inside = in_now.  A step is taken
+ *               from the last frame the id was SEEN in, however many unseen frames lie between.
+ *   d born      inside = in_now, every set bit counts as entered, dwell[z] = 1 for the set bits and 0 for the others (all
+ *               16), last = the anchor; no line test.
+ *   e unseen    a live slot that survives: dwell[z] += 1 (saturating) for its set bits z < zone_n: the person is taken to be
+ *               still there.
+ *   f freed     every set bit z < zone_n counts as exited; id = gap = inside = 0, dwell[z] = 0 (all 16); last keeps its bytes.
+ *               Rules d and f keep zone_total[z].entered - zone_total[z].exited == the live slots with bit z after every frame.
+ *   g outputs   out_slot[b][p] = the person's slot, -1 for everybody else and rows >= P; out_inside[b][p] = in_now[p] of every
+ *               listed person, tracked or not, 0 for rows >= P; out_zone[b][z] = (occupancy: the listed people with bit z;
+ *               entered and exited of this frame; loitering: the live slots after the frame with dwell[z] >= loiter);
+ *               out_line[b][l] = (forward, backward) of this frame; zeros for z >= zone_n and l >= line_n.
+ * Every output byte is written on every call; an image that is not processed gets -1 in out_slot and 0 elsewhere.
+ * Precondition: the positive ids of one image are distinct (the tracker's are); otherwise the result is unspecified, but no
+ * access leaves the buffers.
+ *
+ * One launch on `stream` (one workgroup per stream), no allocation, no host synchronisation, no D2H: it can be captured
+ * into a graph.  No atomics -- each stream's workgroup owns its words; two runs give identical bytes.  PPN_E_INVALID before
+ * anything is launched for: a NULL cfg, geom, st, table, state pointer, input or output (only xy and n_frames may be NULL); K
+ * outside 1..PPN_MAX_KP; max_gap < 0; an unknown anchor; loiter < 1; streams, frames or max_humans < 1.  PPN_E_UNSUPPORTED:
+ * max_humans > PPN_MATCH_MAX_PEOPLE.
+ */
+#define PPN_ZONE_SLOTS 64             /* tracked ids per stream: as many as the tracker has tracks */
+#define PPN_ZONE_MAX 16               /* zones per stream    */
+#define PPN_ZONE_MAX_VERT 8           /* vertices per zone   */
+#define PPN_LINE_MAX 16               /* lines per stream    */
+#define PPN_ZONE_FLAG_SLOT_OVERFLOW 1
+#define PPN_ZONE_ANCHOR_CENTER 0      /* the centre of the root box (or the smoothed centre) */
+#define PPN_ZONE_ANCHOR_BOTTOM 1      /* the middle of the root box's lower edge: the feet   */
+
+typedef struct ppn_zone_geom {        /* device pointers, filled from the host */
+    const int32_t* zone_n;   /* [S]                                   */
+    const int32_t* zone_nv;  /* [S][16]                               */
+    const float* zone_xy;    /* [S][16][8][2]  (x, y)                 */
+    const int32_t* line_n;   /* [S]                                   */
+    const float* line_xy;    /* [S][16][4]     (ax, ay, bx, by)       */
+} ppn_zone_geom;
+
+typedef struct ppn_zone_cfg {
+    int32_t K;        /* keypoints, keypoint 0 = the instance (root) box       */
+    int32_t max_gap;  /* >= 0: frames an id is held without being seen          */
+    int32_t anchor;   /* PPN_ZONE_ANCHOR_*                                      */
+    int32_t loiter;   /* >= 1: frames of dwell from which a person loiters      */
+} ppn_zone_cfg;
+
+typedef struct ppn_zone_state {       /* device pointers; ALL ZERO BYTES = fresh */
+    int32_t* id;          /* [S][64]      0 = free                                           */
+    int32_t* gap;         /* [S][64]      frames since the id was last seen                  */
+    uint32_t* inside;     /* [S][64]      bit z: in zone z at the last update                */
+    int32_t* dwell;       /* [S][64][16]  consecutive frames in zone z                       */
+    float* last;          /* [S][64][2]   anchor (x, y) of the last frame the id was seen in */
+    int32_t* zone_total;  /* [S][16][2]   (entered, exited) since the reset                  */
+    int32_t* line_total;  /* [S][16][2]   (forward, backward) since the reset                */
+    int32_t* flags;       /* [S]          OR of PPN_ZONE_FLAG_*, cleared by the caller       */
+} ppn_zone_state;
+
+int ppn_zone_update(const ppn_zone_cfg* cfg, const ppn_zone_geom* geom, const ppn_zone_state* st, const int32_t* count,
+                    const int32_t* kp_cell, const float* bbox, const int32_t* ids, const float* xy /* or NULL */,
+                    int32_t streams, int32_t frames, int32_t max_humans,
+                    const int32_t* n_frames /* [S] or NULL = `frames` each */, int32_t* out_slot /* [B][max_humans] */,
+                    uint32_t* out_inside /* [B][max_humans] */, int32_t* out_zone /* [B][16][4] */,
+                    int32_t* out_line /* [B][16][2] */, void* stream);
+
+/*
  * Horizontal-flip test-time averaging (no counterpart in the reference), csrc/tta.hip: the network sees a frame and its
  * left-right mirror image, the second head is mapped back and averaged with the first, and only then the decode runs.
  * Geometry as in ppn_decode_cfg; the heads are f32 [batch, C, H, W] NCHW with C = 6K + E*sH*sW: six unary groups resp, conf,

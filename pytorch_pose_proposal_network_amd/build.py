@@ -70,6 +70,10 @@ SOURCES = [
     # clips.hip is bit-exact with a NumPy restatement in the normalised clips: (x - cx) / s as one subtraction and one
     # IEEE-rounded divide
     ("clips.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
+    # zones.hip is bit-exact with a NumPy restatement at the zone and line boundaries: the edge interpolation of the polygon
+    # test, (xj - xi) * (ay - yi) / (yj - yi) + xi, uncontracted with an IEEE-rounded divide, and the two cross products
+    # (the side of a line, the segment test) as two products and one subtraction
+    ("zones.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
 ]
 
 

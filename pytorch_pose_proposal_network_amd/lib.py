@@ -20,6 +20,8 @@ PPN_TRACK_SLOTS, PPN_TRACK_MAX_DET = 64, 256                                # pp
 PPN_TRACK_FLAG_DET_OVERFLOW, PPN_TRACK_FLAG_SLOT_OVERFLOW = 1, 2
 PPN_CLIP_SLOTS, PPN_CLIP_MAX_LEN = 64, 256                                  # ppn_clip_push / ppn_clip_gather (csrc/clips.hip)
 PPN_CLIP_NORM_NONE, PPN_CLIP_NORM_ROOT, PPN_CLIP_FLAG_SLOT_OVERFLOW = 0, 1, 1
+PPN_ZONE_SLOTS, PPN_ZONE_MAX, PPN_ZONE_MAX_VERT, PPN_LINE_MAX = 64, 16, 8, 16  # ppn_zone_update (csrc/zones.hip)
+PPN_ZONE_FLAG_SLOT_OVERFLOW, PPN_ZONE_ANCHOR_CENTER, PPN_ZONE_ANCHOR_BOTTOM = 1, 0, 1
 PPN_PIX_NV12, PPN_PIX_I420, PPN_PIX_YUYV = 0, 1, 2                         # ppn_ingest_desc.format (csrc/ingest.hip)
 PPN_PIX_BGR24 = 3                                                           # ppn_ingest_windows only
 PPN_MAX_WINDOWS, PPN_MERGE_MAX_CAND = 16, 512                               # ppn_merge_windows (csrc/windows.hip)
@@ -161,6 +163,21 @@ class ClipCfg(C.Structure):
 class ClipState(C.Structure):
     """ppn_clip_state: device pointers."""
     _fields_ = [(n, C.c_void_p) for n in ("id", "gap", "len", "ref", "mask", "ring", "pos", "flags")]
+
+
+class ZoneGeom(C.Structure):
+    """ppn_zone_geom (csrc/zones.hip): device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in ("zone_n", "zone_nv", "zone_xy", "line_n", "line_xy")]
+
+
+class ZoneCfg(C.Structure):
+    """ppn_zone_cfg."""
+    _fields_ = [(n, C.c_int32) for n in ("K", "max_gap", "anchor", "loiter")]
+
+
+class ZoneState(C.Structure):
+    """ppn_zone_state: device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in ("id", "gap", "inside", "dwell", "last", "zone_total", "line_total", "flags")]
 
 
 class IngestDesc(C.Structure):
@@ -360,6 +377,8 @@ _SIGNATURES.update({
     "ppn_clip_push": (C.c_int, [C.POINTER(ClipCfg), C.POINTER(ClipState)] + [C.c_void_p] * 6 + [C.c_int32] * 3 +
                       [C.c_void_p] * 3),
     "ppn_clip_gather": (C.c_int, [C.POINTER(ClipCfg), C.POINTER(ClipState), C.c_int32] + [C.c_void_p] * 4),
+    "ppn_zone_update": (C.c_int, [C.POINTER(ZoneCfg), C.POINTER(ZoneGeom), C.POINTER(ZoneState)] + [C.c_void_p] * 5 +
+                        [C.c_int32] * 3 + [C.c_void_p] * 6),
     "ppn_ingest_windows": (C.c_int, [C.POINTER(IngestDesc), C.POINTER(WindowLayout), C.c_void_p]),
     "ppn_merge_windows": (C.c_int, [C.POINTER(MergeCfg), C.POINTER(WindowLayout)] + [C.c_void_p] * 4 + [C.c_int32] +
                           [C.c_void_p] * 6),

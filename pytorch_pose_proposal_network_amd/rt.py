@@ -292,6 +292,17 @@ def inference_batch_clips(frames_u8: torch.Tensor, model: PoseProposalNet, track
     return res, tracks, rows, clips.gather() if gather else None
 
 
+def inference_batch_zones(frames_u8: torch.Tensor, model: PoseProposalNet, tracker, zones, decoder: Optional[D.Decoder] = None,
+                          detection_thresh: float = 0.15, flip_tta: bool = False, merger=None):
+    """inference_batch_tracked plus the zones and counting lines, all on the device: -> (DecodeResult, track.TrackResult,
+    zones.ZoneResult).  `zones` is a zones.Zones of the tracker's streams, frames and max_humans (give it max_gap = the
+    tracker's max_age and reset the two together: then its slots are the live tracks); its geometry is in the network's
+    input pixels here, and it takes the tracker's smoothed centres.  For big frames, Zones.update takes the results of
+    inference_windows plus Tracker.update as they are: then the geometry is in frame pixels.  Nothing is read back."""
+    res, tracks = inference_batch_tracked(frames_u8, model, tracker, decoder, detection_thresh, flip_tta, merger)
+    return res, tracks, zones.update(res, tracks)
+
+
 def inference_windows(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNet, layout, decoder: Optional[D.Decoder] = None,
                       merger=None, detection_thresh: float = 0.15, size=384, flip: bool = False, matrix: str = "bt601",
                       full_range: bool = False, pitch: Optional[int] = None, merge_thr: float = 0.3,
