@@ -1257,6 +1257,101 @@ int ppn_zone_update(const ppn_zone_cfg* cfg, const ppn_zone_geom* geom, const pp
                     int32_t* out_line /* [B][16][2] */, void* stream);
 
 /*
+ * The monitoring overlay (no counterpart in the reference), csrc/render.hip: track ids, zones, counting lines and their
+ * counts painted by the rasteriser of ppn_draw_humans, onto RGB frames (ppn_draw_scene) or raw NV12 / I420 / YUYV surfaces
+ * (ppn_draw_scene_yuv), from ppn_track_update's and ppn_zone_update's results as they lie on the device: nothing is read
+ * back, and the colours of a zone or line follow this frame's occupancy and crossings.  tests/overlay_ref.py restates the
+ * rules below in NumPy; kernel and restatement agree on every byte.  Not built: alpha-blended zone fill, trails, text other
+ * than the 16 glyphs.
+ *
+ * The picture is ppn_draw_humans' (resp. ppn_draw_humans_yuv's) with a second list of primitives per image painted after
+ * all people and before the grid; everything else -- the surface rule, in place / out of place, pitches, limits -- is
+ * theirs.  Image b = s * frames + t is frame t of stream s (ppn_track_update's layout); an image with t >= n_frames[s]
+ * gets no overlay (NULL n_frames: every image is processed).  The list has a fixed slot per item, the slot order being the
+ * paint order: zone z = 0..15 (edges 0..7, plate, text), then line l = 0..15 (segment, tick, plate, text), then person
+ * p = 0 .. min(count, max_humans) - 1 (root outline, plate, text).  T is truncation toward zero of an f32; a value v is
+ * usable iff |v| < 2^20 (NaN is not); every f32 step is one IEEE operation rounded on its own.
+ *
+ * Primitives (NORMATIVE).  A line is ppn_draw_humans' limb: PIL's width-2 line between integer end points, one pixel for a
+ * zero vector.  A fill is the inclusive pixel box [x0, y0, x1, y1].  A text is n <= 16 glyphs of the font below at (x0, y0)
+ * with scale s: pixel (x, y) is covered iff, with u = x - x0, v = y - y0 (integer division): u >= 0, 0 <= v < 7 s,
+ * c = u / (6 s) < n, col = (u % (6 s)) / s < 5, and bit 4 - col of FONT[code_c][v / s] is set.  A label at (x0, y0) is the
+ * plate, the fill [x0 - 1, y0 - 1, x0 + 6 s n - s, y0 + 7 s] in `plate`, drawn only when cfg.plates is set, and then the
+ * text in `text`.  Numbers are decimal without leading zeros; a count v is printed as min(max(v, 0), 999999), an id in
+ * full.  The font, seven row bytes per glyph code from the top row down, bit 4 the leftmost column:
+ *     FONT  0   0E 11 13 15 19 11 0E     '0'
+ *     FONT  1   04 0C 04 04 04 04 0E     '1'
+ *     FONT  2   0E 11 01 02 04 08 1F     '2'
+ *     FONT  3   1F 02 04 02 01 11 0E     '3'
+ *     FONT  4   02 06 0A 12 1F 02 02     '4'
+ *     FONT  5   1F 10 1E 01 01 11 0E     '5'
+ *     FONT  6   06 08 10 1E 11 11 0E     '6'
+ *     FONT  7   1F 01 02 04 08 08 08     '7'
+ *     FONT  8   0E 11 11 0E 11 11 0E     '8'
+ *     FONT  9   0E 11 11 0F 01 02 0C     '9'
+ *     FONT 10   00 04 04 00 04 04 00     ':'
+ *     FONT 11   00 00 00 1F 00 00 00     '-'
+ *     FONT 12   0A 0A 1F 0A 1F 0A 0A     '#'
+ *     FONT 13   00 00 00 00 00 00 00     ' '
+ *     FONT 14   00 00 00 00 00 00 00     spare
+ *     FONT 15   00 00 00 00 00 00 00     spare
+ *
+ * The zone part (all of geom's tables, out_zone, out_line and line_total given; all NULL: no zone part).  zone_n and line_n
+ * are clamped to 0..16 and a vertex number nv to 0..8 as ppn_zone_update clamps them.
+ *   zone z     drawn iff z < zone_n[s], nv >= 3 and every coordinate of its nv vertices is usable.  Edge i < nv: the line
+ *              from (T(x_i), T(y_i)) to (T(x_j), T(y_j)), j = (i + 1) mod nv, in `alert` if out_zone[b][z][3] > 0 (somebody
+ *              loiters), else `active` if out_zone[b][z][0] > 0 (occupied), else zone_colour[z].  Label: the occupancy
+ *              out_zone[b][z][0] at (T(x_0) + 3, T(y_0) + 3).
+ *   line l     drawn iff l < line_n[s] and ax, ay, bx, by are usable.  Colour: `active` if out_line[b][l][0] +
+ *              out_line[b][l][1] > 0 (wrapping i32), else line_colour[l].  Segment: the line from (T(ax), T(ay)) to
+ *              (T(bx), T(by)).  Tick, on the side a forward crossing ends on: dx = bx - ax, dy = by - ay,
+ *              len = sqrtf(dx * dx + dy * dy), mx = (ax + bx) / 2, my = (ay + by) / 2, q = tick / len,
+ *              ex = mx + (-dy) * q, ey = my + dx * q: the line from (T(mx), T(my)) to (T(ex), T(ey)); omitted when
+ *              len == 0 or ex or ey is not usable.  Label "F:B" at (T(mx) + 3, T(my) + 3), the cumulative totals AS OF
+ *              THIS FRAME: F = line_total[s][l][0] - the sum over t' > t of out_line[s * frames + t'][l][0] in wrapping
+ *              i32 arithmetic, B likewise on [1].  line_total holds the totals after the whole batch; taking the later
+ *              frames' crossings off again gives each frame of a batch of several frames per stream its own running
+ *              count, so the numbers on consecutive frames step when the crossing happens, not at the batch's start.
+ * The id part (ids given; NULL: no id part).  Person p < min(max(count[b], 0), max_humans) with ids[b][p] > 0 whose root
+ * keypoint takes part in ppn_draw_humans' picture (kp_cell[b][p][0] >= 0, its four box values usable): the root's two
+ * outlines again, in id_colour[id & 15], and the id as a label at x0 = T(xmin), y0 = T(ymin) - 7 s - 1, or, when
+ * y0 - 1 < 0 (the plate would leave the frame at the top), at y0 = T(ymin) + 3, inside the box.
+ * With neither part the call is ppn_draw_humans (ppn_draw_humans_yuv).
+ *
+ * workspace: ppn_draw_scene_workspace_bytes(cfg, batch, max_humans) bytes, 16-byte aligned: the people's records and 48
+ * bytes per overlay slot (224 + 3 max_humans per image) behind them.  Still two launches on `stream` -- one setup kernel
+ * writes both lists --, no allocation, no host synchronisation: capturable into a graph.  For a raw surface the overlay's
+ * colours are converted on the host with ppn_rgb_to_yuv's rule, like the palette.  PPN_E_INVALID before any launch:
+ * everything ppn_draw_humans (ppn_draw_humans_yuv) refuses; a NULL overlay or in; scale outside 1..4; frames < 1; batch no
+ * multiple of frames; a negative or non-finite tick; some but not all pointers of the zone part.
+ */
+typedef struct ppn_overlay_cfg {
+    int32_t frames;                  /* frames per stream in the batch, >= 1 */
+    int32_t scale;                   /* glyph pixel size s, 1..4            */
+    float tick;                      /* length of a line's direction tick in pixels, finite, >= 0 */
+    int32_t plates;                  /* draw the plates under the texts     */
+    uint8_t zone_colour[16][4], line_colour[16][4], id_colour[16][4];        /* r, g, b, unused */
+    uint8_t active[4], alert[4], text[4], plate[4];
+} ppn_overlay_cfg;
+
+typedef struct ppn_overlay_in {      /* device pointers */
+    const int32_t* ids;              /* [B][max_humans]  ppn_track_update's out_id, or NULL                     */
+    ppn_zone_geom geom;              /* the tables ppn_zone_update was given                                    */
+    const int32_t* out_zone;         /* [B][16][4]       ppn_zone_update's outputs of this batch                */
+    const int32_t* out_line;         /* [B][16][2]                                                              */
+    const int32_t* line_total;       /* [S][16][2]       ppn_zone_state.line_total after that update            */
+    const int32_t* n_frames;         /* [S] or NULL                                                             */
+} ppn_overlay_in;
+
+size_t ppn_draw_scene_workspace_bytes(const ppn_draw_cfg* cfg, int32_t batch, int32_t max_humans); /* 0 on a bad argument */
+int ppn_draw_scene(const ppn_draw_cfg* cfg, const ppn_overlay_cfg* overlay, const ppn_overlay_in* in, const uint8_t* src,
+                   uint8_t* dst, int32_t batch, int32_t height, int32_t width, const int32_t* count, const int32_t* kp_cell,
+                   const float* bbox, int32_t max_humans, void* workspace, void* stream);
+int ppn_draw_scene_yuv(const ppn_draw_cfg* cfg, const ppn_overlay_cfg* overlay, const ppn_overlay_in* in,
+                       const ppn_yuv_surface* src, const ppn_yuv_surface* dst, int32_t batch, const int32_t* count,
+                       const int32_t* kp_cell, const float* bbox, int32_t max_humans, void* workspace, void* stream);
+
+/*
  * Horizontal-flip test-time averaging (no counterpart in the reference), csrc/tta.hip: the network sees a frame and its
  * left-right mirror image, the second head is mapped back and averaged with the first, and only then the decode runs.
  * Geometry as in ppn_decode_cfg; the heads are f32 [batch, C, H, W] NCHW with C = 6K + E*sH*sW: six unary groups resp, conf,

@@ -17,4 +17,4 @@ bool pack_tiled_enabled() {
 }  // namespace ppn
 
 extern "C" const char* ppn_last_error(void) { return ppn::error_buffer(); }
-extern "C" int ppn_version(void) { return 1; }
+extern "C" int ppn_version(void) { return 2; }

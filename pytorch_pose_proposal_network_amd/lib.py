@@ -180,6 +180,19 @@ class ZoneState(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("id", "gap", "inside", "dwell", "last", "zone_total", "line_total", "flags")]
 
 
+class OverlayCfg(C.Structure):
+    """ppn_overlay_cfg (csrc/render.hip: ppn_draw_scene)."""
+    _fields_ = [("frames", C.c_int32), ("scale", C.c_int32), ("tick", C.c_float), ("plates", C.c_int32)] + [
+        (n, (C.c_uint8 * 4) * 16) for n in ("zone_colour", "line_colour", "id_colour")] + [
+        (n, C.c_uint8 * 4) for n in ("active", "alert", "text", "plate")]
+
+
+class OverlayIn(C.Structure):
+    """ppn_overlay_in: device pointers."""
+    _fields_ = [("ids", C.c_void_p), ("geom", ZoneGeom)] + [
+        (n, C.c_void_p) for n in ("out_zone", "out_line", "line_total", "n_frames")]
+
+
 class IngestDesc(C.Structure):
     """ppn_ingest_desc (csrc/ingest.hip: ppn_ingest_yuv)."""
     _fields_ = [(n, C.c_int32) for n in ("format", "batch", "src_h", "src_w", "pitch", "pitch_c")] + [
@@ -368,6 +381,13 @@ _SIGNATURES.update({
     "ppn_rgb_to_yuv": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),    # host pointers
     "ppn_draw_humans_yuv": (C.c_int, [C.POINTER(DrawCfg), C.POINTER(YuvSurface), C.POINTER(YuvSurface), C.c_int32,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ppn_draw_scene_workspace_bytes": (C.c_size_t, [C.POINTER(DrawCfg), C.c_int32, C.c_int32]),
+    "ppn_draw_scene": (C.c_int, [C.POINTER(DrawCfg), C.POINTER(OverlayCfg), C.POINTER(OverlayIn), C.c_void_p, C.c_void_p,
+                                 C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                 C.c_void_p]),
+    "ppn_draw_scene_yuv": (C.c_int, [C.POINTER(DrawCfg), C.POINTER(OverlayCfg), C.POINTER(OverlayIn), C.POINTER(YuvSurface),
+                                     C.POINTER(YuvSurface), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p, C.c_void_p]),
     "ppn_pckh_match": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_float] + [C.c_void_p] * 5),
     "ppn_tta_merge": (C.c_int, [C.POINTER(TtaCfg), C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4),

@@ -13,7 +13,9 @@ rt_test.inference does and ``inference_batch_drawn`` the drawn batch, both paint
 datatest.py:162-232).  ``inference_batch_tracked`` / ``inference_tracked`` add what the reference's loop lacks: ids that follow
 a person from frame to frame (track.py), again without reading the people lists back.  ``inference_windows`` runs a big raw
 frame as overlapping windows of the batch and joins the people in frame pixels on the device (windows.py);
-``inference_windows_drawn`` paints them straight onto the raw frames (render.Renderer.draw_yuv); ``inference_crops`` cuts
+``inference_windows_drawn`` paints them straight onto the raw frames (render.Renderer.draw_yuv);
+``inference_batch_zones_drawn`` adds track ids, zones, counting lines and their counts to the picture (render.Overlay);
+``inference_crops`` cuts
 every detected person out of the raw frame as a fixed-size picture for a following model (crops.py).
 """
 from __future__ import annotations
@@ -303,6 +305,28 @@ def inference_batch_zones(frames_u8: torch.Tensor, model: PoseProposalNet, track
     return res, tracks, zones.update(res, tracks)
 
 
+def inference_batch_zones_drawn(frames_u8: torch.Tensor, model: PoseProposalNet, tracker, zones, overlay=None, renderer=None,
+                                out: Optional[torch.Tensor] = None, decoder: Optional[D.Decoder] = None,
+                                detection_thresh: float = 0.15, visbbox: bool = False, gridOn: bool = False,
+                                flip_tta: bool = False, merger=None):
+    """inference_batch_zones plus the monitoring picture, all on the device: -> (DecodeResult, track.TrackResult,
+    zones.ZoneResult, drawn u8 frames).  The people, their track ids, the zones and lines with this frame's occupancy,
+    crossings and running totals are painted onto the frames by ``render.Renderer`` with `overlay` (a render.Overlay whose
+    `frames` is the tracker's; None: ``render.Overlay(frames=tracker.frames)``).  `out` as in render.Renderer (None: a new
+    tensor, `frames_u8` itself: in place); pass a Decoder and a render.Renderer to allocate nothing per call.  Nothing is
+    read back."""
+    from . import render as R
+    res, tracks, zr = inference_batch_zones(frames_u8, model, tracker, zones, decoder, detection_thresh, flip_tta, merger)
+    if overlay is None:
+        overlay = R.Overlay(frames=tracker.frames)
+    if renderer is None:
+        renderer = R.Renderer(frames_u8.shape[0], res.max_humans, frames_u8.device)
+    outW = frames_u8.shape[2] // 16
+    drawn = renderer(frames_u8, res, visbbox=visbbox, gridOn=gridOn, out=out, outsize=(outW, frames_u8.shape[1] // 16),
+                     overlay=overlay, tracks=tracks, zones=zones, zone_result=zr)
+    return res, tracks, zr, drawn
+
+
 def inference_windows(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNet, layout, decoder: Optional[D.Decoder] = None,
                       merger=None, detection_thresh: float = 0.15, size=384, flip: bool = False, matrix: str = "bt601",
                       full_range: bool = False, pitch: Optional[int] = None, merge_thr: float = 0.3,
@@ -339,22 +363,36 @@ def inference_windows(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNe
 def inference_windows_drawn(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNet, layout, decoder: Optional[D.Decoder] = None,
                             merger=None, detection_thresh: float = 0.15, size=384, flip: bool = False, matrix: str = "bt601",
                             full_range: bool = False, pitch: Optional[int] = None, merge_thr: float = 0.3, fuse: bool = True,
-                            renderer=None, out: Optional[torch.Tensor] = None, visbbox: bool = False):
+                            renderer=None, out: Optional[torch.Tensor] = None, visbbox: bool = False, overlay=None,
+                            tracker=None, zones=None):
     """inference_windows plus the drawing, all on the device: the merged people painted straight onto the raw frames they
     were found in (``render.Renderer.draw_yuv``: NV12 / I420 / YUYV surfaces without an RGB intermediate, `matrix` and
     `full_range` naming the surface's colours as they do for the ingest; "bgr" through the RGB rasteriser) ->
     (DecodeResult, drawn raw frames).  `out` as in draw_yuv (None: a new tensor, `raw` itself: in place); pass a Decoder, a
     windows.WindowMerger and a render.Renderer of (F, merged max_humans) to allocate nothing per call.  Nothing is read back.
-    ``flip=True`` raises ValueError: the people of a turned frame do not lie on the unturned surface."""
+    ``flip=True`` raises ValueError: the people of a turned frame do not lie on the unturned surface.
+    With `overlay` (a render.Overlay) the monitoring picture is painted too and the return value is (DecodeResult, drawn,
+    TrackResult or None, ZoneResult or None): `tracker` (a track.Tracker) is updated with the merged people and labels them
+    with their ids, `zones` (a zones.Zones, which needs the tracker; its geometry in FRAME pixels) is updated and drawn."""
     from . import render as R
     if flip:
         raise ValueError("inference_windows_drawn: flip=True gives the people of the turned frame, which do not lie on `raw`")
+    if overlay is None and (tracker is not None or zones is not None):
+        raise ValueError("inference_windows_drawn: tracker and zones are drawn by an overlay: pass overlay=render.Overlay(...)")
+    if zones is not None and tracker is None:
+        raise ValueError("inference_windows_drawn: zones count tracked people: pass the tracker too")
     res = inference_windows(raw, fmt, src_hw, model, layout, decoder, merger, detection_thresh, size, False, matrix,
                             full_range, pitch, merge_thr, fuse)
     if renderer is None:
         renderer = R.Renderer(raw.shape[0], res.max_humans, raw.device)
-    return res, renderer.draw_yuv(raw, fmt, src_hw, res, visbbox=visbbox, out=out, pitch=pitch, matrix=matrix,
-                                  full_range=full_range)
+    if overlay is None:
+        return res, renderer.draw_yuv(raw, fmt, src_hw, res, visbbox=visbbox, out=out, pitch=pitch, matrix=matrix,
+                                      full_range=full_range)
+    tracks = tracker.update(res) if tracker is not None else None
+    zr = zones.update(res, tracks) if zones is not None else None
+    drawn = renderer.draw_yuv(raw, fmt, src_hw, res, visbbox=visbbox, out=out, pitch=pitch, matrix=matrix,
+                              full_range=full_range, overlay=overlay, tracks=tracks, zones=zones, zone_result=zr)
+    return res, drawn, tracks, zr
 
 
 def inference_crops(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNet, cropper, layout=None, tracker=None,

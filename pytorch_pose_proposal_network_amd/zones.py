@@ -17,8 +17,8 @@ tracker is installed for, without reading its result back.
 
 Coordinates are in the pixels of the DecodeResult the update is given: the network's input pixels after rt.inference_batch,
 frame pixels after rt.inference_windows.  The rules (include/ppn.h, ppn_zone_update) are restated in NumPy by
-tests/zones_ref.py.  Not built: drawing zones and lines, per-keypoint anchors such as ankles, more than 16 zones or lines or
-8 vertices, hysteresis against a person dithering on a line (net forward - backward stays right), MultiLaneInference
+tests/zones_ref.py.  Zones, lines and their counts are drawn by render.Overlay.  Not built: per-keypoint anchors such as ankles,
+more than 16 zones or lines or 8 vertices, hysteresis against a person dithering on a line (net forward - backward stays right), MultiLaneInference
 integration.
 """
 from __future__ import annotations
