@@ -1257,6 +1257,110 @@ int ppn_zone_update(const ppn_zone_cfg* cfg, const ppn_zone_geom* geom, const pp
                     int32_t* out_line /* [B][16][2] */, void* stream);
 
 /*
+ * Re-identification by appearance on the device (no counterpart in the reference), csrc/reid.hip: a small integer colour
+ * descriptor per person, read straight from the raw frame (ppn_people_descr), and a gallery per stream that gives every
+ * person a PERSISTENT id which survives a change of track id when the appearance matches somebody recently lost
+ * (ppn_reid_update).  tests/reid_ref.py restates both entries in NumPy; kernels and restatement agree on bytes.  Nothing here
+ * claims an identification accuracy: the descriptor is a colour histogram and the default threshold of the Python layer a
+ * guess, not a measurement.  Not built: a learned embedding, identities across streams, more than 128 entries per stream, a
+ * motion model.
+ *
+ * ppn_people_descr: `src` is one raw surface as ppn_redact_yuv takes it (NV12, I420, YUYV and PPN_PIX_BGR24, any pitch and
+ * plane alignment, frame f at f * frame_stride; matrix and full_range are checked but not used: no colour is converted),
+ * roi i32 [F][R][4] = (y0, x0, h, w) and status i32 [F][R] the DEVICE tables ppn_people_rois writes -> descr u16
+ * [F][R][PPN_DESCR_LEN] and valid i32 [F][R].  All integer, so the bytes do not depend on any order:
+ *   judging     a slot is described iff status == PPN_ROI_OK and the rectangle is good by ppn_ingest_rois' rule: y0 >= 0,
+ *               x0 >= 0, h >= 1, w >= 1, y0 + h <= height, x0 + w <= width, x0 and w even in a YUV format, y0 and h even in
+ *               NV12 / I420.  The table is data the host never sees, so it is judged on the device, per workgroup and before
+ *               any read.  Any other slot gets valid = 0 and an all-zero descriptor, and the surface is not read for it.
+ *   samples     a fixed grid of PPN_DESCR_ROWS x PPN_DESCR_COLS points per rectangle, whatever its size: sample (i, j) is
+ *               the source pixel y = y0 + ((2 i + 1) * h) / 192, x = x0 + ((2 j + 1) * w) / 64 (integer division).  A
+ *               rectangle smaller than the grid repeats pixels; the largest index is (191 * h) / 192 < h.
+ *   channels    YUV formats: (c0, c1, c2) = (Y, U, V) of the pixel, the chroma being the sample the pixel shares:
+ *               (y >> 1, x >> 1) in NV12 / I420, (y, x >> 1) in YUYV.  BGR24: (c0, c1, c2) = (G, B, R).
+ *   bins        8 per channel: c >> 5 for Y and the three BGR channels, (min(max(c, 64), 191) - 64) >> 4 for U and V.
+ *   bands       band = i / 32: roughly head and shoulders, torso, legs of a "people" rectangle.
+ *   descriptor  descr[band][channel][bin] = the number of the band's samples in the bin: 3 x 3 x 8 = PPN_DESCR_LEN counts;
+ *               each (band, channel) histogram of a valid slot sums to 1024.  valid = 1.
+ * Every entry of descr and valid is written on every call.  One workgroup per (frame, slot), one launch on `stream`, no
+ * global atomics, no workspace, no allocation, no host synchronisation: it can be captured into a graph, and two runs give
+ * identical bytes.  PPN_E_INVALID before any launch for: everything ppn_redact_yuv refuses of a single surface; a NULL roi,
+ * status, descr or valid; max_rois < 1; frames < 1 or frames * max_rois > 65535.
+ *
+ * ppn_reid_update: the gallery.  Batch layout and n_frames are ppn_track_update's: image b = s * frames + t is frame t of
+ * stream s, only t < n_frames[s] is processed (a negative n_frames[s] counts as 0, NULL means `frames` each), the frames of a
+ * stream go in ascending t within the call, and a stream without a processed frame keeps every state byte and its flags
+ * word.  The similarity of two descriptors is their histogram intersection, the sum of min(a[k], b[k]) over the 72 counts:
+ * an integer in 0..PPN_REID_SIM_MAX.  descr [B][max_rois][72] and valid [B][max_rois] are ppn_people_descr's outputs with
+ * F = B and R = max_rois, ids [B][max_humans] ppn_track_update's out_id.  One processed frame, with P = min(max(count[b], 0),
+ * max_humans); person p < P TAKES PART iff ids[b][p] > 0 and HAS A DESCRIPTOR iff p < max_rois && valid[b][p] != 0; an
+ * entry is LIVE iff pid != 0; all comparisons are made on the state as it was before the frame:
+ *   1 bound    a live entry whose tid equals a participant's id: the person continues that pid, lost = 0.  With a
+ *              descriptor: descr = the new one if n == 0, otherwise per count
+ *              descr = (old * ((1 << shift) - 1) + new + ((1 << shift) >> 1)) >> shift; n = min(n + 1, 65535).  Without
+ *              one descr and n keep their bytes.
+ *   2 relink   the participants whose id no live entry holds and who have a descriptor, in ascending p (descending root
+ *              score): the candidates are the live entries not bound in step 1, not yet claimed in this frame, with n > 0
+ *              and min_lost <= lost <= memory.  The winner has the largest similarity, then the smallest lost, then the
+ *              lowest index.  It is CLAIMED iff its similarity >= thr: tid = the person's id (the track id it held is
+ *              forgotten), lost = 0, the descriptor blended and n counted as in step 1.
+ *   3 age      every live entry neither bound nor claimed: lost += 1; when lost > memory it is FREED: pid = tid = lost =
+ *              n = 0 (descr keeps its bytes: n == 0 guards them).
+ *   4 births   the participants still without an entry, in ascending p, take the free entries in ascending index, the
+ *              ones freed in step 3 included: pid = ++last_pid[s], tid = the id, lost = 0; descr = the person's and n = 1,
+ *              or n = 0 without a descriptor.  Without a free entry the person's out_pid is -1 and
+ *              PPN_REID_FLAG_SLOT_OVERFLOW is set.  Pids are never reused.
+ *   5 outputs  out_pid[b][p] = the person's pid, -1 for non-participants, overflow and rows >= P; out_sim[b][p] = the
+ *              similarity a person relinked with in step 2, -1 for everybody else; out_live[b] = the live entries after the
+ *              frame.  An image that is not processed gets -1 everywhere.  Every entry is written on every call.
+ * Invariant: after every frame the tids of a stream's live entries are distinct, hence the positive out_pid of an image are
+ * distinct -- the precondition ppn_clip_push and ppn_zone_update put on ids, so out_pid can stand in for the tracker's ids.
+ * Precondition: the positive ids of one image are distinct (the tracker's are); otherwise the result is unspecified, but no
+ * access leaves the buffers.
+ *
+ * One launch on `stream` (one workgroup per stream), no allocation, no host synchronisation, no D2H, no atomics: it can be
+ * captured into a graph and two runs give identical bytes.  PPN_E_INVALID before anything is launched for: a NULL cfg, st,
+ * state pointer, input or output (only n_frames may be NULL); thr outside 0..PPN_REID_SIM_MAX; min_lost < 1; memory < 0;
+ * shift outside 0..4; max_rois < 1; streams, frames or max_humans < 1.  PPN_E_UNSUPPORTED: max_humans > PPN_MATCH_MAX_PEOPLE.
+ */
+#define PPN_DESCR_ROWS 96             /* sample rows per rectangle                            */
+#define PPN_DESCR_COLS 32             /* sample columns per rectangle                         */
+#define PPN_DESCR_BANDS 3
+#define PPN_DESCR_BINS 8
+#define PPN_DESCR_LEN 72              /* 3 bands x 3 channels x 8 bins                        */
+#define PPN_REID_SLOTS 128            /* gallery entries per stream                           */
+#define PPN_REID_SIM_MAX 9216         /* 9 histograms of 1024 samples                         */
+#define PPN_REID_FLAG_SLOT_OVERFLOW 1
+
+int ppn_people_descr(const ppn_yuv_surface* src, int32_t frames, const int32_t* roi /* [F][R][4] */,
+                     const int32_t* status /* [F][R] */, int32_t max_rois, uint16_t* descr /* [F][R][72] */,
+                     int32_t* valid /* [F][R] */, void* stream);
+
+typedef struct ppn_reid_cfg {
+    int32_t thr;       /* 0..9216: the similarity from which a lost entry is taken up again   */
+    int32_t min_lost;  /* >= 1: processed frames an entry must have been unseen for           */
+    int32_t memory;    /* >= 0: processed frames an entry is kept unseen                      */
+    int32_t shift;     /* 0..4: the new descriptor's weight in the blend is 2^-shift          */
+    int32_t max_rois;  /* >= 1: the R of descr and valid                                      */
+} ppn_reid_cfg;
+
+typedef struct ppn_reid_state {       /* device pointers; ALL ZERO BYTES = fresh */
+    int32_t* pid;        /* [S][128]      0 = free                                          */
+    int32_t* tid;        /* [S][128]      the track id the entry is bound to                */
+    int32_t* lost;       /* [S][128]      processed frames since it was seen                */
+    int32_t* n;          /* [S][128]      descriptors blended in so far, at most 65535      */
+    uint16_t* descr;     /* [S][128][72]                                                    */
+    int32_t* last_pid;   /* [S]           the last pid handed out                           */
+    int32_t* flags;      /* [S]           OR of PPN_REID_FLAG_*, cleared by the caller      */
+} ppn_reid_state;
+
+int ppn_reid_update(const ppn_reid_cfg* cfg, const ppn_reid_state* st, const int32_t* count /* [B] */,
+                    const int32_t* ids /* [B][max_humans] */, const uint16_t* descr /* [B][max_rois][72] */,
+                    const int32_t* valid /* [B][max_rois] */, int32_t streams, int32_t frames, int32_t max_humans,
+                    const int32_t* n_frames /* [S] or NULL = `frames` each */, int32_t* out_pid /* [B][max_humans] */,
+                    int32_t* out_sim /* [B][max_humans] */, int32_t* out_live /* [B] */, void* stream);
+
+/*
  * The monitoring overlay (no counterpart in the reference), csrc/render.hip: track ids, zones, counting lines and their
  * counts painted by the rasteriser of ppn_draw_humans, onto RGB frames (ppn_draw_scene) or raw NV12 / I420 / YUYV surfaces
  * (ppn_draw_scene_yuv), from ppn_track_update's and ppn_zone_update's results as they lie on the device: nothing is read

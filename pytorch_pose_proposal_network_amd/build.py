@@ -74,6 +74,9 @@ SOURCES = [
     # test, (xj - xi) * (ay - yi) / (yj - yi) + xi, uncontracted with an IEEE-rounded divide, and the two cross products
     # (the side of a line, the segment test) as two products and one subtraction
     ("zones.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
+    # reid.hip has no float arithmetic at all (integer histograms and their intersection): nothing to contract or to round,
+    # and no MFMA code, hence no NOSLP
+    ("reid.hip", []),
 ]
 
 

@@ -30,7 +30,9 @@ PPN_ROI_OK, PPN_ROI_EMPTY, PPN_ROI_DEGENERATE, PPN_ROI_BAD = 0, 1, 2, 4        #
 PPN_ROI_MODE_ROOT, PPN_ROI_MODE_PEOPLE = 0, 1                               # ppn_roi_cfg.mode (csrc/crops.hip)
 PPN_REDACT_FALLBACK_PERSON, PPN_REDACT_FALLBACK_NONE, PPN_REDACT_FLAG_BAD_BOX = 0, 1, 1   # ppn_redact_cells (csrc/redact.hip)
 PPN_REDACT_MOSAIC, PPN_REDACT_FILL = 0, 1                                   # ppn_redact_cfg.mode
-PPN_STEM_RAW_S2 = 1 << 16          # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
+PPN_DESCR_ROWS, PPN_DESCR_COLS, PPN_DESCR_BANDS, PPN_DESCR_BINS, PPN_DESCR_LEN = 96, 32, 3, 8, 72   # ppn_people_descr (csrc/reid.hip)
+PPN_REID_SLOTS, PPN_REID_SIM_MAX, PPN_REID_FLAG_SLOT_OVERFLOW = 128, 9216, 1  # ppn_reid_update
+PPN_STEM_RAW_S2 = 1 << 16         # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
 
 
 def PPN_STEM_IO(internal: int, out: int) -> int:
@@ -178,6 +180,16 @@ class ZoneCfg(C.Structure):
 class ZoneState(C.Structure):
     """ppn_zone_state: device pointers."""
     _fields_ = [(n, C.c_void_p) for n in ("id", "gap", "inside", "dwell", "last", "zone_total", "line_total", "flags")]
+
+
+class ReIdCfg(C.Structure):
+    """ppn_reid_cfg (csrc/reid.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("thr", "min_lost", "memory", "shift", "max_rois")]
+
+
+class ReIdState(C.Structure):
+    """ppn_reid_state: device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in ("pid", "tid", "lost", "n", "descr", "last_pid", "flags")]
 
 
 class OverlayCfg(C.Structure):
@@ -407,6 +419,9 @@ _SIGNATURES.update({
     "ppn_redact_cells": (C.c_int, [C.POINTER(RedactCellsCfg)] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     "ppn_redact_yuv": (C.c_int, [C.POINTER(RedactCfg), C.POINTER(YuvSurface), C.POINTER(YuvSurface), C.c_int32, C.c_void_p,
                                  C.c_void_p]),
+    "ppn_people_descr": (C.c_int, [C.POINTER(YuvSurface), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3),
+    "ppn_reid_update": (C.c_int, [C.POINTER(ReIdCfg), C.POINTER(ReIdState)] + [C.c_void_p] * 4 + [C.c_int32] * 3 +
+                        [C.c_void_p] * 5),
 })
 
 EXPORTS = tuple(_SIGNATURES)

@@ -470,6 +470,43 @@ def inference_redacted(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalN
     return (res, done) if tracker is None else (res, done, tracks)
 
 
+def inference_reid(raw: torch.Tensor, fmt: str, src_hw, model: PoseProposalNet, tracker, reid, layout=None,
+                   decoder: Optional[D.Decoder] = None, merger=None, detection_thresh: float = 0.15, size=384,
+                   flip: bool = False, pitch: Optional[int] = None, merge_thr: float = 0.3, fuse: bool = True):
+    """Detect and track the people of raw frames and give them persistent ids by appearance (reid.py), all on the device:
+    ingest -> forward -> fused decode (-> window merge when `layout`, a windows.WindowLayout of `src_hw`, is given:
+    ``inference_windows``) -> `tracker`.update -> rectangles -> descriptors from `raw` -> gallery.  `reid` is a reid.ReId of
+    streams x frames = F images on `src_hw` / `fmt` whose ``coords_hw`` is the space the people come out in: the frame with
+    a layout, the network input (`size`) without; it names the surface's matrix and range, which the ingest uses too, and
+    carries the gallery from call to call.  Returns ``(DecodeResult, TrackResult, ReIdResult)``; pass a Decoder (and a
+    WindowMerger) to allocate nothing per call.  Nothing is read back.  ``flip=True`` raises ValueError: the people of a
+    turned frame do not lie on the unturned surface."""
+    from . import windows as W
+    if flip:
+        raise ValueError("inference_reid: flip=True gives the people of the turned frame, which do not lie on `raw`")
+    H, Wd = int(src_hw[0]), int(src_hw[1])
+    h, w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    space = (H, Wd) if layout is not None else (h, w)
+    if reid.src_hw != (H, Wd) or reid.fmt != fmt or reid.coords_hw != space or reid.batch != raw.shape[0]:
+        raise ValueError(f"the ReId takes {reid.batch} {reid.fmt} frames of {reid.src_hw} with boxes in {reid.coords_hw}; "
+                         f"the call has {raw.shape[0]} {fmt} frames of {(H, Wd)} and people in {space}")
+    matrix, full_range = reid.matrix, reid.full_range
+    if layout is not None:
+        res = inference_windows(raw, fmt, src_hw, model, layout, decoder, merger, detection_thresh, size, False, matrix,
+                                full_range, pitch, merge_thr, fuse)
+    else:
+        frames = raw.shape[0]
+        buf = model.input_buffer(frames, h, w, True, True)
+        W.ingest_windows(raw, fmt, W.WindowLayout((H, Wd), [(0, 0, H, Wd)]), (h, w), buf, False, matrix, full_range, pitch)
+        unary, keys = model.forward_u8(buf, fused_decode=True)
+        if decoder is None:
+            decoder = D.Decoder(frames, (unary.shape[2], unary.shape[3]), (h, w), model.local_grid_size, detection_thresh,
+                                device=unary.device)
+        res = decoder.decode_fused(unary, keys)
+    tracks = tracker.update(res)
+    return res, tracks, reid.reid(raw, res, tracks, pitch=pitch)
+
+
 def inference_tracked(image, model: PoseProposalNet, outsize, local_grid_size, tracker, detection_thresh: float = 0.15,
                       flip_tta: bool = False):
     """``inference`` for the frames of one video: returns ``(humans, scores, ids)`` -- the reference-style lists of

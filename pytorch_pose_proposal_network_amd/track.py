@@ -9,8 +9,9 @@ every frame on its own) over csrc/track.hip.
                                                     smoothed keypoint centres, and per image the number of live tracks.
 
 The rules (greedy matching by close keypoints, then IoU; exponential smoothing; ageing; births) are include/ppn.h's,
-ppn_track_update; tests/track_ref.py restates them in NumPy.  Not built: a motion model, re-identification by appearance,
-colouring drawn people by id, InferencePipeline / MultiLaneInference integration, more than 64 tracks per stream.
+ppn_track_update; tests/track_ref.py restates them in NumPy.  Re-identification by appearance -- an id that
+survives the death of a track -- is reid.py's, which takes a TrackResult.  Not built: a motion model, colouring drawn people
+by id, InferencePipeline / MultiLaneInference integration, more than 64 tracks per stream.
 """
 from __future__ import annotations
 
