@@ -1361,6 +1361,88 @@ int ppn_reid_update(const ppn_reid_cfg* cfg, const ppn_reid_state* st, const int
                     int32_t* out_sim /* [B][max_humans] */, int32_t* out_live /* [B] */, void* stream);
 
 /*
+ * Actions from skeleton clips (no counterpart in the reference), csrc/stgcn.hip: the forward pass of ST-GCN (Yan, Xiong,
+ * Lin 2018), one person per clip, eval mode, exact f32, on what ppn_clip_gather wrote.  tests/stgcn_ref.py restates the
+ * function from the unfolded state dict; actions.py folds every BatchNorm and bias on the host (f64, rounded once).
+ *
+ * Layout.  `capacity` = streams * PPN_CLIP_SLOTS clips at most.  The n = *n_active ACTIVE clips lie first in every activation
+ * buffer, f32 [n][t][v][c], channels last; what follows them is never read or written.  All four entry points launch for the
+ * capacity and read *n_active on the device: a workgroup whose clip index is >= *n_active exits at once, so a captured
+ * graph replays on any population, zero included.  One output element is summed in one fixed order that depends on nothing
+ * but the descriptor: a clip's values do not depend on the other clips or on its place in the list.  No atomics.
+ *
+ * ppn_stgcn_input (uses dtype, K, T).  Slot j = s * 64 + i of x f32 [S][64][3][T][K], ids and length i32 [S][64] is ACTIVE
+ * iff ids[j] != 0 && length[j] >= min_len.  With r(j) the number of active slots before j: rank[j] = r(j) if active else
+ * -1; active[r(j)] = j; active[m] = -1 for m >= n; *n_active = n.  Every byte of active i32 [S*64], rank i32 [S*64] and
+ * n_active is written.  For an active slot x0[r][t][v][c] = fmaf(x[j][c][t][v], scale[v*3+c], shift[v*3+c]) (data_bn
+ * folded; zero-padded frames are not special-cased).
+ *
+ * ppn_stgcn_gcn.  x [n][T][K][cin] -> out [n][T][K][cout]:
+ *   y[t][w][p][ci] = sum_v x[t][v][ci] * adj[p][v][w]          (MFMA: an fmaf chain from 0, v ascending, zeros past K; adj
+ *                                                                f32 [P][K][K] already multiplied by the edge importance)
+ *   z[t][w][c]     = sum_{ci chunk of 16} sum_p sum_{ci in chunk} W[p*cout+c][ci] * y[t][w][p][ci]     (MFMA, chunks ascending)
+ *   out            = max(fmaf(z, s0[c], t0[w][c]), 0)          t0 f32 [K][cout] carries the gcn bias passed through adj
+ * cin is padded to a multiple of 16 inside the kernel (x is read with its own pitch cin; the packed weights hold zeros).
+ * w is packed in fragment order: float4 number ((ct * ncc + cc) * P + p) * 64 + g * 16 + col, component j, is
+ * W[p*cout + ct*16 + col][cc*16 + 4*g + j], ct < cout/16, cc < ncc = ceil(cin/16), zero where the input channel is >= cin.
+ *
+ * ppn_stgcn_tcn.  u [n][T][K][cout] (the gcn's output), x [n][T][K][cin] (the block's input; NULL for PPN_STGCN_RES_NONE)
+ * -> out [n][To][K][cout], To = (T - 1) / stride + 1:
+ *   z[t'][v][c] = sum_{ci chunk} sum_{k<9} sum_{ci} Wt[c][ci][k] * u[t'*stride - 4 + k][v][ci]
+ *                 (+ sum_{ci chunk} sum_{ci} Wr'[c][ci] * x[t'*stride][v][ci]   for PPN_STGCN_RES_PROJ, Wr' = Wr * sr / s3)
+ *   out         = max(fmaf(z, s3[c], t3[c]) (+ x[t'][v][c] for PPN_STGCN_RES_IDENTITY), 0)
+ * A tap whose time step lies outside [0, T) OF ITS OWN CLIP contributes zero.  w: float4 number ((ct * ncc + cc) * 9 + k) *
+ * 64 + g * 16 + col, component j, is Wt[ct*16 + col][cc*16 + 4*g + j][k], ncc = cout/16; behind these (cout/16) * ncc * 9 *
+ * 64 float4, for PROJ, float4 number (ct * nrc + rc) * 64 + g * 16 + col is Wr'[ct*16 + col][rc*16 + 4*g + j], nrc =
+ * ceil(cin/16), zero past cin.
+ *
+ * ppn_stgcn_head (uses dtype, K, T = the last block's To, cout = its channels).  For slot j with r = rank[j] >= 0:
+ * pooled[c] = (sum over (t, v) ascending of x[r][t][v][c]) / (T*K); logits[j][m] = fmaf chain over c ascending from b[m] with
+ * w f32 [c][num_class]; label[j] = the lowest index of the largest logit.  rank[j] < 0: zeros and -1.  Every byte of logits
+ * f32 [S][64][num_class] and label i32 [S][64] is written.
+ *
+ * Each entry point is one launch on `stream`, no allocation, no host synchronisation, no D2H.  PPN_E_UNSUPPORTED before any
+ * launch: dtype != PPN_F32 (a 16-bit mode is not built).  PPN_E_INVALID: a NULL descriptor or pointer (x of the tcn may be
+ * NULL without a shortcut); K outside 1..PPN_MAX_KP; T outside 1..PPN_CLIP_MAX_LEN; P outside 1..PPN_STGCN_MAX_P; cout not a
+ * multiple of 16 in 16..PPN_STGCN_MAX_C; cin neither 3 nor such a multiple; stride not 1 or 2; an unknown residual; an
+ * identity shortcut with cin != cout or stride 2; num_class outside 1..PPN_STGCN_MAX_CLASS; streams outside
+ * 1..PPN_STGCN_MAX_STREAMS; a capacity that is not streams * 64; a weight, scale, shift or activation pointer the kernels
+ * read or write as float4 that is not 16-byte aligned.
+ */
+#define PPN_STGCN_MAX_P 3
+#define PPN_STGCN_MAX_C 256
+#define PPN_STGCN_MAX_CLASS 1024
+#define PPN_STGCN_MAX_STREAMS 1024
+#define PPN_STGCN_RES_NONE 0
+#define PPN_STGCN_RES_IDENTITY 1
+#define PPN_STGCN_RES_PROJ 2
+
+typedef struct ppn_stgcn_desc {
+    int32_t dtype;     /* PPN_F32; the field is there so that a 16-bit mode can follow */
+    int32_t K;         /* joints                                                       */
+    int32_t P;         /* partitions of the adjacency, 1..3                            */
+    int32_t T;         /* time steps of the stage's input                              */
+    int32_t cin;       /* the block's input channels: 3 or a multiple of 16            */
+    int32_t cout;      /* the block's output channels: a multiple of 16, <= 256        */
+    int32_t stride;    /* temporal stride of the block: 1 or 2                         */
+    int32_t residual;  /* PPN_STGCN_RES_*                                              */
+} ppn_stgcn_desc;
+
+int ppn_stgcn_input(const ppn_stgcn_desc* d, const float* x /* [S][64][3][T][K] */, const int32_t* ids, const int32_t* length,
+                    int32_t streams, int32_t min_len, const float* scale /* [K*3] */, const float* shift /* [K*3] */,
+                    int32_t* active /* [S*64] */, int32_t* n_active /* [1] */, int32_t* rank /* [S*64] */,
+                    float* x0 /* [S*64][T][K][3] */, void* stream);
+int ppn_stgcn_gcn(const ppn_stgcn_desc* d, const float* x, const float* w, const float* adj /* [P][K][K] */,
+                  const float* s0 /* [cout] */, const float* t0 /* [K][cout] */, const int32_t* n_active, int32_t capacity,
+                  float* out, void* stream);
+int ppn_stgcn_tcn(const ppn_stgcn_desc* d, const float* u, const float* x /* or NULL */, const float* w,
+                  const float* s3 /* [cout] */, const float* t3 /* [cout] */, const int32_t* n_active, int32_t capacity,
+                  float* out, void* stream);
+int ppn_stgcn_head(const ppn_stgcn_desc* d, int32_t num_class, const float* x, const float* w /* [c][num_class] */,
+                   const float* b /* [num_class] */, const int32_t* rank /* [S*64] */, int32_t streams,
+                   float* logits /* [S][64][num_class] */, int32_t* label /* [S][64] */, void* stream);
+
+/*
  * The monitoring overlay (no counterpart in the reference), csrc/render.hip: track ids, zones, counting lines and their
  * counts painted by the rasteriser of ppn_draw_humans, onto RGB frames (ppn_draw_scene) or raw NV12 / I420 / YUYV surfaces
  * (ppn_draw_scene_yuv), from ppn_track_update's and ppn_zone_update's results as they lie on the device: nothing is read

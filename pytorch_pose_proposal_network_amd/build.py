@@ -77,6 +77,8 @@ SOURCES = [
     # reid.hip has no float arithmetic at all (integer histograms and their intersection): nothing to contract or to round,
     # and no MFMA code, hence no NOSLP
     ("reid.hip", []),
+    # stgcn.hip runs f32 MFMAs: NOSLP like the convolutions; its results are held to derived bounds, not to bytes
+    ("stgcn.hip", NOSLP),
 ]
 
 

@@ -32,6 +32,8 @@ PPN_REDACT_FALLBACK_PERSON, PPN_REDACT_FALLBACK_NONE, PPN_REDACT_FLAG_BAD_BOX = 
 PPN_REDACT_MOSAIC, PPN_REDACT_FILL = 0, 1                                   # ppn_redact_cfg.mode
 PPN_DESCR_ROWS, PPN_DESCR_COLS, PPN_DESCR_BANDS, PPN_DESCR_BINS, PPN_DESCR_LEN = 96, 32, 3, 8, 72   # ppn_people_descr (csrc/reid.hip)
 PPN_REID_SLOTS, PPN_REID_SIM_MAX, PPN_REID_FLAG_SLOT_OVERFLOW = 128, 9216, 1  # ppn_reid_update
+PPN_STGCN_MAX_P, PPN_STGCN_MAX_C, PPN_STGCN_MAX_CLASS, PPN_STGCN_MAX_STREAMS = 3, 256, 1024, 1024   # ppn_stgcn_* (csrc/stgcn.hip)
+PPN_STGCN_RES_NONE, PPN_STGCN_RES_IDENTITY, PPN_STGCN_RES_PROJ = 0, 1, 2      # ppn_stgcn_desc.residual
 PPN_STEM_RAW_S2 = 1 << 16         # ppn_*stem012_dt dtype flag: out_raw holds only the even (row, column) pixels
 
 
@@ -190,6 +192,11 @@ class ReIdCfg(C.Structure):
 class ReIdState(C.Structure):
     """ppn_reid_state: device pointers."""
     _fields_ = [(n, C.c_void_p) for n in ("pid", "tid", "lost", "n", "descr", "last_pid", "flags")]
+
+
+class StgcnDesc(C.Structure):
+    """ppn_stgcn_desc (csrc/stgcn.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "K", "P", "T", "cin", "cout", "stride", "residual")]
 
 
 class OverlayCfg(C.Structure):
@@ -422,6 +429,10 @@ _SIGNATURES.update({
     "ppn_people_descr": (C.c_int, [C.POINTER(YuvSurface), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3),
     "ppn_reid_update": (C.c_int, [C.POINTER(ReIdCfg), C.POINTER(ReIdState)] + [C.c_void_p] * 4 + [C.c_int32] * 3 +
                         [C.c_void_p] * 5),
+    "ppn_stgcn_input": (C.c_int, [C.POINTER(StgcnDesc)] + [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 7),
+    "ppn_stgcn_gcn": (C.c_int, [C.POINTER(StgcnDesc)] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 2),
+    "ppn_stgcn_tcn": (C.c_int, [C.POINTER(StgcnDesc)] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 2),
+    "ppn_stgcn_head": (C.c_int, [C.POINTER(StgcnDesc), C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3),
 })
 
 EXPORTS = tuple(_SIGNATURES)

@@ -294,6 +294,21 @@ def inference_batch_clips(frames_u8: torch.Tensor, model: PoseProposalNet, track
     return res, tracks, rows, clips.gather() if gather else None
 
 
+def inference_batch_actions(frames_u8: torch.Tensor, model: PoseProposalNet, tracker, clips, actions,
+                            decoder: Optional[D.Decoder] = None, detection_thresh: float = 0.15, flip_tta: bool = False,
+                            merger=None):
+    """inference_batch_clips plus the action model, all on the device: -> (DecodeResult, track.TrackResult, clips.ClipRows,
+    clips.ClipBatch, actions.ActionResult).  `actions` is an actions.ActionModel of the clips' streams, length and K; it
+    classifies every live clip that holds at least its ``min_len`` frames, the others get label -1.  Nothing is read back
+    (``ActionResult.to_host()`` is the one read-back, when the labels are wanted on the host)."""
+    if (actions.streams, actions.length, actions.spec.K) != (clips.streams, clips.length, clips.K):
+        raise ValueError(f"the ActionModel takes {actions.streams} streams of clips [3, {actions.length}, {actions.spec.K}], "
+                         f"the PoseClips hand out {clips.streams} of [3, {clips.length}, {clips.K}]")
+    res, tracks, rows, batch = inference_batch_clips(frames_u8, model, tracker, clips, decoder, detection_thresh, flip_tta,
+                                                     merger)
+    return res, tracks, rows, batch, actions(batch)
+
+
 def inference_batch_zones(frames_u8: torch.Tensor, model: PoseProposalNet, tracker, zones, decoder: Optional[D.Decoder] = None,
                           detection_thresh: float = 0.15, flip_tta: bool = False, merger=None):
     """inference_batch_tracked plus the zones and counting lines, all on the device: -> (DecodeResult, track.TrackResult,
