@@ -1402,7 +1402,7 @@ int ppn_reid_update(const ppn_reid_cfg* cfg, const ppn_reid_state* st, const int
  * f32 [S][64][num_class] and label i32 [S][64] is written.
  *
  * Each entry point is one launch on `stream`, no allocation, no host synchronisation, no D2H.  PPN_E_UNSUPPORTED before any
- * launch: dtype != PPN_F32 (a 16-bit mode is not built).  PPN_E_INVALID: a NULL descriptor or pointer (x of the tcn may be
+ * launch: dtype != PPN_F32 (PPN_F16: ppn_stgcn16_* below).  PPN_E_INVALID: a NULL descriptor or pointer (x of the tcn may be
  * NULL without a shortcut); K outside 1..PPN_MAX_KP; T outside 1..PPN_CLIP_MAX_LEN; P outside 1..PPN_STGCN_MAX_P; cout not a
  * multiple of 16 in 16..PPN_STGCN_MAX_C; cin neither 3 nor such a multiple; stride not 1 or 2; an unknown residual; an
  * identity shortcut with cin != cout or stride 2; num_class outside 1..PPN_STGCN_MAX_CLASS; streams outside
@@ -1418,7 +1418,7 @@ int ppn_reid_update(const ppn_reid_cfg* cfg, const ppn_reid_state* st, const int
 #define PPN_STGCN_RES_PROJ 2
 
 typedef struct ppn_stgcn_desc {
-    int32_t dtype;     /* PPN_F32; the field is there so that a 16-bit mode can follow */
+    int32_t dtype;     /* PPN_F32 for ppn_stgcn_*, PPN_F16 for ppn_stgcn16_*                  */
     int32_t K;         /* joints                                                       */
     int32_t P;         /* partitions of the adjacency, 1..3                            */
     int32_t T;         /* time steps of the stage's input                              */
@@ -1441,6 +1441,69 @@ int ppn_stgcn_tcn(const ppn_stgcn_desc* d, const float* u, const float* x /* or 
 int ppn_stgcn_head(const ppn_stgcn_desc* d, int32_t num_class, const float* x, const float* w /* [c][num_class] */,
                    const float* b /* [num_class] */, const int32_t* rank /* [S*64] */, int32_t streams,
                    float* logits /* [S][64][num_class] */, int32_t* label /* [S][64] */, void* stream);
+
+/*
+ * The same forward pass with IEEE half storage, csrc/stgcn16.hip: v_mfma_f32_16x16x32_f16 with f32 accumulation.  The four
+ * entry points take the ppn_stgcn_desc with dtype == PPN_F16 and the argument lists of their f32 counterparts; activations and
+ * packed weights are IEEE half behind void pointers; the scale and shift tables (scale, shift, s0, t0, s3, t3), the
+ * classifier's w and b and the logits stay f32.  The layout, launch and determinism rules above hold unchanged: one launch per
+ * entry point for the capacity, *n_active read on the device, a workgroup past it exits at once, no allocation, no
+ * synchronisation, no read-back, no atomics, no split reductions; one output element is summed in one fixed order that depends
+ * on nothing but the descriptor, so a clip's bits depend neither on the other clips nor on its place.  tests/stgcn16_ref.py
+ * restates the mode.  "half(v)" is ONE rounding of the f32 value v to nearest even.
+ *
+ * Range.  Conversions do not clamp: a value beyond 65504 becomes inf, and from there on the clip's results are inf or NaN.
+ * ActionModel.half_range_report tells whether a checkpoint's activations fit.
+ *
+ * Depth lanes past the data.  The MFMA's depth step is 32.  A depth lane or row that the data does not cover (a joint
+ * v >= K, a channel >= cin or cout, the pad channel of x0) takes the value 0 in BOTH operands, never what lies behind the row
+ * in memory or LDS: stale half bits can be inf or NaN, and 0 * inf poisons the sum.
+ *
+ * ppn_stgcn16_input.  active, rank and n_active are byte for byte what ppn_stgcn_input writes.  x0 is half [n][T][K][4]:
+ * x0[r][t][v][c] = half(fmaf(x[j][c][t][v], scale[v*3+c], shift[v*3+c])) for c < 3, computed in f32; x0[r][t][v][3] = 0, so
+ * rows are 8 bytes.  A block with cin == 3 (its graph convolution, and a projection shortcut from it) reads its input with
+ * this pitch of 4; every other block with its pitch cin.
+ *
+ * Weights and adjacency.  adj half [P][K][K] is the adjacency already multiplied by the edge importance; it and every packed
+ * weight (W, Wt, Wr' = Wr * sr / s3) are rounded ONCE from the f64 folded value to half, on the host.  A 16-byte unit holds the
+ * 8 halves j = 0..7 of one lane's A fragment, lane = g * 16 + col:
+ *   gcn w:  unit ((ct * ncc + cc) * P + p) * 64 + g * 16 + col, half j, is W[p*cout + ct*16 + col][cc*32 + 8*g + j],
+ *           ct < cout/16, cc < ncc = ceil(cin/32), zero where the input channel is >= cin.
+ *   tcn w:  unit ((ct * ncc + cc) * 9 + k) * 64 + g * 16 + col, half j, is Wt[ct*16 + col][cc*32 + 8*g + j][k], ncc =
+ *           ceil(cout/32), zero where the input channel is >= cout; behind these (cout/16) * ncc * 9 * 64 units, for PROJ, unit
+ *           (ct * nrc + rc) * 64 + g * 16 + col, half j, is Wr'[ct*16 + col][rc*32 + 8*g + j], nrc = ceil(cin/32), zero past cin.
+ *
+ * ppn_stgcn16_gcn.  x half [n][T][K][cin or 4] -> out half [n][T][K][cout]:
+ *   y[t][w][p][ci] = half(sum_v x[t][v][ci] * adj[p][v][w])     (one MFMA over the joints, f32 accumulation, zeros past K)
+ *   z[t][w][c]     = sum_{ci chunk of 32} sum_p sum_{ci in chunk} W[p*cout+c][ci] * y[t][w][p][ci]      (MFMA, f32 accumulation,
+ *                                                                 chunks ascending, p ascending inside a chunk)
+ *   out            = half(max(fmaf(z, s0[c], t0[w][c]), 0))
+ *
+ * ppn_stgcn16_tcn.  u half [n][T][K][cout], x half [n][T][K][cin or 4] (NULL for PPN_STGCN_RES_NONE) -> out half
+ * [n][To][K][cout]: z as in ppn_stgcn_tcn, accumulated in f32 over chunks of 32 channels ascending, the nine taps ascending
+ * inside a chunk, then the projection shortcut's chunks; o = fmaf(z, s3[c], t3[c]) in f32 (+ float(x[t'][v][c]) in f32 for
+ * PPN_STGCN_RES_IDENTITY); out = half(max(o, 0)).  A tap whose time step lies outside [0, T) OF ITS OWN CLIP contributes zero.
+ *
+ * ppn_stgcn16_head.  ppn_stgcn_head reading half x: pooled in f32 in the same order, the same classifier and arg-max; every
+ * byte of logits f32 [S][64][num_class] and label i32 [S][64] is written.
+ *
+ * PPN_E_UNSUPPORTED before any launch: dtype != PPN_F16 (PPN_F32 and PPN_BF16 included).  PPN_E_INVALID: everything
+ * ppn_stgcn_* refuses so, and an x0, x, u, w, s0, t0, s3, t3 or out pointer (x of the tcn: with a shortcut) that is not 16-byte
+ * aligned.
+ */
+int ppn_stgcn16_input(const ppn_stgcn_desc* d, const float* x /* [S][64][3][T][K] */, const int32_t* ids, const int32_t* length,
+                      int32_t streams, int32_t min_len, const float* scale /* [K*3] */, const float* shift /* [K*3] */,
+                      int32_t* active /* [S*64] */, int32_t* n_active /* [1] */, int32_t* rank /* [S*64] */,
+                      void* x0 /* half [S*64][T][K][4] */, void* stream);
+int ppn_stgcn16_gcn(const ppn_stgcn_desc* d, const void* x, const void* w, const void* adj /* half [P][K][K] */,
+                    const float* s0 /* [cout] */, const float* t0 /* [K][cout] */, const int32_t* n_active, int32_t capacity,
+                    void* out, void* stream);
+int ppn_stgcn16_tcn(const ppn_stgcn_desc* d, const void* u, const void* x /* or NULL */, const void* w,
+                    const float* s3 /* [cout] */, const float* t3 /* [cout] */, const int32_t* n_active, int32_t capacity,
+                    void* out, void* stream);
+int ppn_stgcn16_head(const ppn_stgcn_desc* d, int32_t num_class, const void* x, const float* w /* [c][num_class] */,
+                     const float* b /* [num_class] */, const int32_t* rank /* [S*64] */, int32_t streams,
+                     float* logits /* [S][64][num_class] */, int32_t* label /* [S][64] */, void* stream);
 
 /*
  * The monitoring overlay (no counterpart in the reference), csrc/render.hip: track ids, zones, counting lines and their

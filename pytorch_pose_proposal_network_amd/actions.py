@@ -1,11 +1,15 @@
 """Actions from skeleton clips on the device (no counterpart in the reference) over csrc/stgcn.hip: the forward pass of ST-GCN
 (Yan, Xiong, Lin 2018: "Spatial Temporal Graph Convolutional Networks for Skeleton-Based Action Recognition"), one person per
-clip, eval mode, exact f32, on the ``ClipBatch`` that ``PoseClips.gather()`` wrote.
+clip, eval mode, on the ``ClipBatch`` that ``PoseClips.gather()`` wrote: exact f32, or opt-in ``compute_dtype="float16"`` over
+csrc/stgcn16.hip -- IEEE half storage of activations, weights and adjacency, v_mfma_f32_16x16x32_f16 with f32 accumulation,
+scales, shifts, classifier and logits in f32 (rules: ppn_stgcn16_* in include/ppn.h; restatement: tests/stgcn16_ref.py).
+Conversions do not clamp: ``ActionModel.half_range_report(batch)`` tells whether a checkpoint's activations fit into half.
 
 * ``skeleton_graph(edges, K, center)``        -- the "spatial" partition of the skeleton at hop 1, f32 [3, K, K] (NumPy).
 * ``STGCNSpec`` / ``stgcn_spec(name, n)``     -- the network as data: blocks (cin, cout, stride, residual); "paper", "tiny".
 * ``random_state_dict(spec, seed)``           -- weights under the key names of the public ST-GCN implementation, for tests.
 * ``fold(spec, state_dict)``                  -- every BatchNorm and bias folded into scale and shift, in f64.
+* ``pack_gcn16`` / ``pack_tcn16``                -- the half packed orders of ppn_stgcn16_gcn / ppn_stgcn16_tcn.
 * ``ActionModel(spec, state_dict, streams, length)`` -- owns the folded, packed weights and every intermediate buffer for
                                                  streams * 64 clips; ``model(batch)`` is 2 + 2 x blocks launches on the
                                                  current stream -> ``ActionResult``; no allocation, no synchronisation,
@@ -13,7 +17,7 @@ clip, eval mode, exact f32, on the ``ClipBatch`` that ``PoseClips.gather()`` wro
 
 The rules are include/ppn.h's (ppn_stgcn_*); tests/stgcn_ref.py restates the function from the unfolded state dict.  NO
 trained checkpoint ships and NO CLAIM is made about recognition accuracy: the tests hold the arithmetic to the restatement
-on random weights, nothing more.  Not built: a 16-bit mode, two people per clip, training, softmax, MultiLaneInference
+on random weights, nothing more.  Not built: bf16, two people per clip, training, softmax, MultiLaneInference
 integration.
 """
 from __future__ import annotations
@@ -281,6 +285,32 @@ def pack_tcn(wt: np.ndarray, wr: Optional[np.ndarray]) -> np.ndarray:
     return np.concatenate(parts)
 
 
+def pack_gcn16(wg: np.ndarray) -> np.ndarray:
+    """wg [P, cout, cin] f64 -> half in the fragment order of ppn_stgcn16_gcn: [ct][cc][p][g][col][j], 8 halves j per lane,
+    the input channel cc * 32 + 8 g + j, zero past cin; every value rounded once from f64."""
+    w = _pad_to(wg, 2, 32)
+    P, cout, cp = w.shape
+    w = w.reshape(P, cout // 16, 16, cp // 32, 4, 8).transpose(1, 3, 0, 4, 2, 5)
+    return np.ascontiguousarray(w).astype(np.float16).reshape(-1)
+
+
+def pack_tcn16(wt: np.ndarray, wr: Optional[np.ndarray]) -> np.ndarray:
+    """wt [cout, cout, 9] (and wr [cout, cin]) f64 -> half in the fragment order of ppn_stgcn16_tcn: [ct][cc][k][g][col][j],
+    then [ct][rc][g][col][j]; input channels in chunks of 32, zero past cout / cin."""
+    cout = wt.shape[0]
+    w = _pad_to(wt, 1, 32)
+    w = w.reshape(cout // 16, 16, w.shape[1] // 32, 4, 8, 9).transpose(0, 2, 5, 3, 1, 4)
+    parts = [np.ascontiguousarray(w).astype(np.float16).reshape(-1)]
+    if wr is not None:
+        r = _pad_to(wr, 1, 32)
+        r = r.reshape(cout // 16, 16, r.shape[1] // 32, 4, 8).transpose(0, 2, 3, 1, 4)
+        parts.append(np.ascontiguousarray(r).astype(np.float16).reshape(-1))
+    return np.concatenate(parts)
+
+
+DTYPES = {"float32": L.PPN_F32, "float16": L.PPN_F16}
+
+
 def desc(K: int, P: int, T: int, cin: int, cout: int, stride: int, residual: str, dtype: int = L.PPN_F32) -> "L.StgcnDesc":
     return L.StgcnDesc(dtype, K, P, T, cin, cout, stride, RESIDUALS[residual])
 
@@ -288,24 +318,41 @@ def desc(K: int, P: int, T: int, cin: int, cout: int, stride: int, residual: str
 class BlockWeights:
     """The device tensors of one folded block, in the layout the kernels read."""
 
-    def __init__(self, b: dict, device):
+    def __init__(self, b: dict, device, dtype: str = "float32"):
         import torch
+        if dtype not in DTYPES:
+            raise ValueError(f"dtype {dtype!r}: one of {sorted(DTYPES)}")
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)                 # noqa: E731
+        self.dtype = dtype
         self.cin, self.cout, self.stride, self.residual = b["cin"], b["cout"], b["stride"], b["residual"]
-        self.adj, self.wg, self.s0, self.t0 = dev(b["adj"]), dev(pack_gcn(b["wg"])), dev(b["s0"]), dev(b["t0"])
-        self.wt, self.s3, self.t3 = dev(pack_tcn(b["wt"], b["wr"])), dev(b["s3"]), dev(b["t3"])
+        self.s0, self.t0, self.s3, self.t3 = dev(b["s0"]), dev(b["t0"]), dev(b["s3"]), dev(b["t3"])
+        if dtype == "float16":                                        # one rounding from the f64 folded value to half
+            h = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)                           # noqa: E731
+            self.adj, self.wg = h(b["adj"].astype(np.float16)), h(pack_gcn16(b["wg"]))
+            self.wt = h(pack_tcn16(b["wt"], b["wr"]))
+        else:
+            self.adj, self.wg, self.wt = dev(b["adj"]), dev(pack_gcn(b["wg"])), dev(pack_tcn(b["wt"], b["wr"]))
+
+
+def _entry(d, w: BlockWeights, stage: str) -> str:
+    """The entry point of `stage` for the descriptor's dtype; weights packed for the other mode are refused here."""
+    if d.dtype != DTYPES[w.dtype]:
+        raise ValueError(f"a descriptor of dtype {d.dtype} with weights packed for {w.dtype}")
+    return ("ppn_stgcn16_" if d.dtype == L.PPN_F16 else "ppn_stgcn_") + stage
 
 
 def launch_gcn(d, w: BlockWeights, x, n_active, capacity: int, out):
-    L.check(L.load().ppn_stgcn_gcn(C.byref(d), x.data_ptr(), w.wg.data_ptr(), w.adj.data_ptr(), w.s0.data_ptr(),
-                                   w.t0.data_ptr(), n_active.data_ptr(), capacity, out.data_ptr(), L.current_stream_ptr()),
-            "ppn_stgcn_gcn")
+    name = _entry(d, w, "gcn")
+    L.check(getattr(L.load(), name)(C.byref(d), x.data_ptr(), w.wg.data_ptr(), w.adj.data_ptr(), w.s0.data_ptr(),
+                                    w.t0.data_ptr(), n_active.data_ptr(), capacity, out.data_ptr(), L.current_stream_ptr()),
+            name)
 
 
 def launch_tcn(d, w: BlockWeights, u, x, n_active, capacity: int, out):
-    L.check(L.load().ppn_stgcn_tcn(C.byref(d), u.data_ptr(), x.data_ptr() if w.residual != "none" else None, w.wt.data_ptr(),
-                                   w.s3.data_ptr(), w.t3.data_ptr(), n_active.data_ptr(), capacity, out.data_ptr(),
-                                   L.current_stream_ptr()), "ppn_stgcn_tcn")
+    name = _entry(d, w, "tcn")
+    L.check(getattr(L.load(), name)(C.byref(d), u.data_ptr(), x.data_ptr() if w.residual != "none" else None, w.wt.data_ptr(),
+                                    w.s3.data_ptr(), w.t3.data_ptr(), n_active.data_ptr(), capacity, out.data_ptr(),
+                                    L.current_stream_ptr()), name)
 
 
 # ---- the public interface -----------------------------------------------------------------------------------------------------
@@ -336,8 +383,13 @@ class ActionModel:
 
     `length` is the clips' T; a slot takes part iff it is live and holds at least `min_len` frames (default: a full clip)."""
 
-    def __init__(self, spec: STGCNSpec, state_dict, streams: int, length: int, min_len: Optional[int] = None, device="cuda"):
+    def __init__(self, spec: STGCNSpec, state_dict, streams: int, length: int, min_len: Optional[int] = None, device="cuda",
+                 compute_dtype: str = "float32"):
         import torch
+        if compute_dtype not in DTYPES:
+            raise ValueError(f"compute_dtype {compute_dtype!r}: one of {sorted(DTYPES)}")
+        self.compute_dtype = compute_dtype
+        dt, half = DTYPES[compute_dtype], compute_dtype == "float16"
         if not 1 <= streams <= L.PPN_STGCN_MAX_STREAMS or not 1 <= length <= L.PPN_CLIP_MAX_LEN:
             raise ValueError(f"{streams} streams of clips of {length}: 1..{L.PPN_STGCN_MAX_STREAMS} and 1..{L.PPN_CLIP_MAX_LEN}")
         if spec.blocks[0][0] != 3:
@@ -351,17 +403,18 @@ class ActionModel:
         i32 = dict(dtype=torch.int32, device=dev)
         K, T = spec.K, self.length
         self.scale, self.shift = (torch.from_numpy(v.astype(np.float32)).to(dev) for v in folded["in"])
-        self.blocks = [BlockWeights(b, dev) for b in folded["blocks"]]
+        self.blocks = [BlockWeights(b, dev, compute_dtype) for b in folded["blocks"]]
         self.wf = torch.from_numpy(np.ascontiguousarray(folded["wf"], np.float32)).to(dev)
         self.bf = torch.from_numpy(folded["bf"].astype(np.float32)).to(dev)
         self.lengths = spec.lengths(T)
-        self.descs = [desc(K, spec.P, t, cin, cout, s, res) for (cin, cout, s, res), t in zip(spec.blocks, self.lengths)]
-        self.d_in = desc(K, spec.P, T, 3, 16, 1, "none")
-        self.d_head = desc(K, spec.P, self.lengths[-1], spec.blocks[-1][1], spec.blocks[-1][1], 1, "none")
+        self.descs = [desc(K, spec.P, t, cin, cout, s, res, dt) for (cin, cout, s, res), t in zip(spec.blocks, self.lengths)]
+        self.d_in = desc(K, spec.P, T, 3, 16, 1, "none", dt)
+        self.d_head = desc(K, spec.P, self.lengths[-1], spec.blocks[-1][1], spec.blocks[-1][1], 1, "none", dt)
         big = max(max(t * cout, to * cout) for (_, cout, _, _), t, to in zip(spec.blocks, self.lengths, self.lengths[1:]))
-        self.x0 = torch.zeros(cap * T * K * 3, **f32)
-        self.u = torch.zeros(cap * big * K, **f32)
-        self.y = [torch.zeros(cap * big * K, **f32) for _ in range(2 if len(spec.blocks) > 1 else 1)]
+        act = dict(dtype=torch.float16 if half else torch.float32, device=dev)
+        self.x0 = torch.zeros(cap * T * K * (4 if half else 3), **act)       # half rows carry a zero pad channel: 8 bytes
+        self.u = torch.zeros(cap * big * K, **act)
+        self.y = [torch.zeros(cap * big * K, **act) for _ in range(2 if len(spec.blocks) > 1 else 1)]
         self.active = torch.full((cap,), -1, **i32)
         self.rank = torch.full((cap,), -1, **i32)
         self.n_active = torch.zeros(1, **i32)
@@ -380,16 +433,42 @@ class ActionModel:
         _dense("batch.ids", batch.ids, (S, SLOTS), torch.int32, dev)
         _dense("batch.length", batch.length, (S, SLOTS), torch.int32, dev)
         lib, st = L.load(), L.current_stream_ptr()
-        L.check(lib.ppn_stgcn_input(C.byref(self.d_in), batch.x.data_ptr(), batch.ids.data_ptr(), batch.length.data_ptr(), S,
-                                    self.min_len, self.scale.data_ptr(), self.shift.data_ptr(), self.active.data_ptr(),
-                                    self.n_active.data_ptr(), self.rank.data_ptr(), self.x0.data_ptr(), st), "ppn_stgcn_input")
+        pre = "ppn_stgcn16_" if self.compute_dtype == "float16" else "ppn_stgcn_"
+        L.check(getattr(lib, pre + "input")(C.byref(self.d_in), batch.x.data_ptr(), batch.ids.data_ptr(), batch.length.data_ptr(),
+                                            S, self.min_len, self.scale.data_ptr(), self.shift.data_ptr(),
+                                            self.active.data_ptr(), self.n_active.data_ptr(), self.rank.data_ptr(),
+                                            self.x0.data_ptr(), st), pre + "input")
         cur = self.x0
         for i, (d, w) in enumerate(zip(self.descs, self.blocks)):
             out = self.y[i % len(self.y)]
             launch_gcn(d, w, cur, self.n_active, self.capacity, self.u)
             launch_tcn(d, w, self.u, cur, self.n_active, self.capacity, out)
             cur = out
-        L.check(lib.ppn_stgcn_head(C.byref(self.d_head), self.spec.num_class, cur.data_ptr(), self.wf.data_ptr(),
-                                   self.bf.data_ptr(), self.rank.data_ptr(), S, self.logits.data_ptr(), self.label.data_ptr(),
-                                   st), "ppn_stgcn_head")
+        L.check(getattr(lib, pre + "head")(C.byref(self.d_head), self.spec.num_class, cur.data_ptr(), self.wf.data_ptr(),
+                                           self.bf.data_ptr(), self.rank.data_ptr(), S, self.logits.data_ptr(),
+                                           self.label.data_ptr(), st), pre + "head")
         return ActionResult(self.logits, self.label, self.active, self.n_active, batch.ids)
+
+    def half_range_report(self, batch) -> dict:
+        """A debugging aid that SYNCHRONISES: runs the call stage by stage and returns {"tensors": {name: largest |value|
+        over the active clips} for "x0" and every block's "block<i>.u" and "block<i>.out", "finite": whether all of them are
+        finite, "limit": 65504.0}.  How a user with a real checkpoint learns that half does not fit: a stored value beyond
+        65504 is inf (the conversions do not clamp).  It reads the buffers the call itself uses; the result of the call is
+        left in place as after ``model(batch)``."""
+        import torch
+        self(batch)                                                  # validates the batch, writes x0 and n_active
+        torch.cuda.synchronize(self.device)
+        n, K = int(self.n_active.item()), self.spec.K
+        peak = lambda t, m: float(t[:m].float().abs().max()) if m else 0.0                               # noqa: E731
+        out = {"x0": peak(self.x0, n * self.length * K * (4 if self.compute_dtype == "float16" else 3))}
+        cur = self.x0
+        for i, (d, w) in enumerate(zip(self.descs, self.blocks)):   # the buffers alternate: each stage is read before reuse
+            dst = self.y[i % len(self.y)]
+            launch_gcn(d, w, cur, self.n_active, self.capacity, self.u)
+            out[f"block{i}.u"] = peak(self.u, n * self.lengths[i] * K * w.cout)
+            launch_tcn(d, w, self.u, cur, self.n_active, self.capacity, dst)
+            out[f"block{i}.out"] = peak(dst, n * self.lengths[i + 1] * K * w.cout)
+            cur = dst
+        torch.cuda.synchronize(self.device)
+        finite = all(np.isfinite(v) for v in out.values())
+        return {"tensors": out, "finite": bool(finite), "limit": 65504.0}

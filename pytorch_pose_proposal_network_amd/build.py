@@ -79,6 +79,8 @@ SOURCES = [
     ("reid.hip", []),
     # stgcn.hip runs f32 MFMAs: NOSLP like the convolutions; its results are held to derived bounds, not to bytes
     ("stgcn.hip", NOSLP),
+    # stgcn16.hip runs f16 MFMAs on half storage: NOSLP; held to derived bounds, and to bytes on exactly representable operands
+    ("stgcn16.hip", NOSLP),
 ]
 
 

@@ -433,6 +433,10 @@ _SIGNATURES.update({
     "ppn_stgcn_gcn": (C.c_int, [C.POINTER(StgcnDesc)] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 2),
     "ppn_stgcn_tcn": (C.c_int, [C.POINTER(StgcnDesc)] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 2),
     "ppn_stgcn_head": (C.c_int, [C.POINTER(StgcnDesc), C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3),
+    "ppn_stgcn16_input": (C.c_int, [C.POINTER(StgcnDesc)] + [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 7),
+    "ppn_stgcn16_gcn": (C.c_int, [C.POINTER(StgcnDesc)] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 2),
+    "ppn_stgcn16_tcn": (C.c_int, [C.POINTER(StgcnDesc)] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 2),
+    "ppn_stgcn16_head": (C.c_int, [C.POINTER(StgcnDesc), C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3),
 })
 
 EXPORTS = tuple(_SIGNATURES)
